@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- pairwise Siegel distances/sec on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--scaling weak|strong] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A *step* is one pass of the hot path (fused Model.forward: gather + distance + metric + scale) over one
@@ -27,6 +28,12 @@ Scaling modes (the pair list shards by triplet, the table is replicated, NO data
                     (DistributedSampler-style interleave rank::N);
   strong            the global batch is fixed at the workload's B and rank r takes pairs r::N of it
                     (B / N pairs per GPU per step: the reference's semantics, train.py:105-110).
+
+A plain run sets up, warms up, times the K steps ONCE and prints the headline record (`value`, `ms_per_step`, the
+configuration).  `--full` adds everything else the benchmark measures and checks: five repetitions of the timed region, the
+device-event repetition, the other scaling mode (N > 1), the bit check against a sequential pass, the per-kernel rooflines with
+live PMC counters, the measured clock, the CPU baseline, parity against the oracle (exit 3 above 1e-4) and the secondary rows.
+`--dump-outputs DIR` writes the distances of the last timed step to DIR/distances.npy.
 
 Prints ONE JSON line on rank 0 (DESIGN.md section 7 explains every field).
 """
@@ -238,6 +245,26 @@ def static_flops_per_valu(kernel_key):
     return None
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+DUMP_SAMPLE = 1 << 21          # values + their positions, float64 each: 32 MiB
+
+
+def dump_outputs(dirname, out, rank, seed):
+    """--dump-outputs: the distances the last timed step returned (this rank's [pairs] float64 output) as
+    <dirname>/distances.npy (rank r > 0: distances_rank<r>.npy).  An output above DUMP_MAX_BYTES is written as a sample of
+    DUMP_SAMPLE entries at positions drawn from `seed` (sorted; the same positions every run with the same arguments), the
+    positions beside it as float64 in distances_sample_index.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    a = out.detach().cpu().numpy().astype(np.float64, copy=False)
+    if a.nbytes > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(seed).choice(a.size, DUMP_SAMPLE, replace=False))
+        np.save(os.path.join(dirname, f"distances_sample_index{suffix}.npy"), idx.astype(np.float64))
+        a = a[idx]
+    np.save(os.path.join(dirname, f"distances{suffix}.npy"), a)
+
+
 def self_launch(nproc, argv, worker=None):
     """`bench.py --gpus N` outside torch.distributed.run: start the N ranks as a child `torch.distributed.run` (never an
     exec: this is called before anything touches the GPU, and the parent never does), relay the ONE JSON line rank 0
@@ -296,10 +323,21 @@ def main():
                          "training steps of the headline / configs[3] / configs[4]) to the record; they are measured by default "
                          "when the headline workload runs on one GPU")
     ap.add_argument("--secondary-budget", type=float, default=150.0, help="seconds the secondary rows may take")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="the K-step timed region is repeated this many times (each repetition: barrier + synchronize, EXACTLY "
-                         "K steps, synchronize; the same warm-up in front of the first); ms_per_step / value are those of the MEDIAN "
-                         "repetition (max over ranks per repetition), ms_per_step_min / _max / _all are in the record")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline figure: 5 repetitions of the timed region, the "
+                         "device-event repetition, the other scaling mode (N > 1), the bit check against a sequential pass, "
+                         "per-kernel rooflines with live PMC counters, the measured clock, the CPU baseline, parity against the "
+                         "oracle and the secondary rows.  Without it the run sets up, warms up, times the K steps once and "
+                         "prints the headline record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the distances the last timed step returned as DIR/distances.npy "
+                         "(float64; rank r > 0 of an N-GPU run: distances_rank<r>.npy; above 64 MB a fixed, seeded sample "
+                         "with its float64 positions in distances_sample_index.npy)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the K-step timed region is repeated this many times (default 1; 5 with --full; each repetition: "
+                         "barrier + synchronize, EXACTLY K steps, synchronize; the same warm-up in front of the first); "
+                         "ms_per_step / value are those of the MEDIAN repetition (max over ranks per repetition), "
+                         "ms_per_step_min / _max / _all are in the record")
     ap.add_argument("--distinct-batches", type=int, default=16)
     ap.add_argument("--graph-nodes", type=int, default=128,
                     help="kernel launches (= steps) captured per hipGraph")
@@ -322,6 +360,8 @@ def main():
                          "j-th batch of them in lexicographic order (the evaluation split, runner.py:124-135) or in "
                          "DistributedSampler order (the training split, train.py:105-110)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus, sys.argv[1:]))
@@ -450,6 +490,7 @@ def main():
                 for rem in sorted({args.steps % self.gn, args.warmup % self.gn} - {0, self.gn}, reverse=True):
                     self.graphs.append((rem, self.capture(rem)))
             self.lists, self.plans = {}, {}
+            self.last_out = None
 
         def step(self, i, fl=None, dst=None):
             o = (self.outs if dst is None else dst)[i % nb]
@@ -508,9 +549,11 @@ def main():
                 p.run(i0, min(spl, k - i0))
 
         def run_steps(self, k):
+            """k steps; self.last_out = the index into self.outs the last of them wrote."""
             if args.launch == "fused":
                 if k > 0:
                     self.run_fused(k)
+                    self.last_out = (k - 1) % nb
                 return
             done = 0
             if spd_pack is not None and k > 0:
@@ -519,8 +562,10 @@ def main():
                 while k - done >= nodes_ and (nodes_ == self.gn or k - done == nodes_):
                     g_.replay()
                     done += nodes_
+                    self.last_out = (nodes_ - 1) % nb       # a graph's node i wrote outs[i % nb]
             while done < k:
                 self.step(done)
+                self.last_out = done % nb
                 done += 1
 
         def time(self, repeats):
@@ -589,12 +634,81 @@ def main():
 
     t_primary = over_ranks(primary.time(args.repeats))
     elapsed = t_primary["elapsed"]
-    timed_out0 = outs[0].clone()            # what the TIMED launches wrote for batch 0: the parity object checks this copy
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs[primary.last_out], rank, args.seed)
     if os.environ.get("SYMPA_BENCH_DUMP"):
         os.makedirs(os.environ["SYMPA_BENCH_DUMP"], exist_ok=True)
         torch.save({"rank": rank, "world": world, "batches": [t.cpu() for t in batches[:min(nb, args.steps)]],
                     "outs": [t.cpu() for t in outs[:min(nb, args.steps)]], "global_pairs": global_pairs},
                    os.path.join(os.environ["SYMPA_BENCH_DUMP"], f"rank{rank}.pt"))
+
+    def headline_record(ranks_seen):
+        """The fields of the headline figure: what the timed region measured, and how it was configured."""
+        value = global_pairs * args.steps / elapsed
+        rec = {
+            "metric": "pairwise Siegel distances/sec (upper, riem, n=4)" if args.workload == "upper-riem-n4-b65536"
+                      else (f"pairwise SPD affine-invariant distances/sec (n={n})" if model == "spd"
+                            else f"pairwise Siegel distances/sec ({model}, {metric}, n={n})"),
+            "value": value, "unit": "pairs/s", "n_gpus": world, "ranks_seen": ranks_seen,
+            "steps": args.steps, "warmup": args.warmup,
+            # the MEDIAN of `repetitions` repetitions of the K-step timed region (each: barrier + synchronize, exactly K steps,
+            # synchronize; max over ranks per repetition); the spread and the first repetition are beside it
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "ms_per_step_min": t_primary["min"] / args.steps * 1e3, "ms_per_step_max": t_primary["max"] / args.steps * 1e3,
+            "ms_per_step_first": t_primary["first"] / args.steps * 1e3,
+            "ms_per_step_all": [x / args.steps * 1e3 for x in t_primary["all"]], "repetitions": len(t_primary["all"]),
+            # fastest and slowest rank of the median repetition (K steps, milliseconds)
+            "elapsed_ranks_ms": {"min": t_primary["rank_min_of_median"] * 1e3, "max": t_primary["rank_max_of_median"] * 1e3},
+            "launch_mode": args.launch, "steps_per_launch": (min(spl, args.steps) if fused is not None else 1),
+            "higher_is_better": True, "scaling": args.scaling,
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": bool(args.full),
+            "config": {"workload": args.workload, "manifold": model, "dist_metric": metric,
+                       "dims": n, "nodes": nodes, "pairs_per_gpu_per_step": my_pairs,
+                       "global_pairs_per_step": global_pairs, "table": args.table, "pairs": args.pairs,
+                       "launch": args.launch,
+                       "api": ("Model.forward_batches(Model.prepare_batches(list of K batches))" if (fused is not None and
+                                                                                spl == ops.MAX_FUSED_BATCHES)
+                               else "ops (C-ABI binding) directly"),
+                       "streams": args.streams,
+                       "parallelism": f"pairs sharded rank::{world}, table replicated, no collective",
+                       "steps_per_launch": min(spl, args.steps) if fused is not None else 1},
+        }
+        rec["value_" + args.scaling] = value
+        rec["ms_per_step_" + args.scaling] = rec["ms_per_step"]
+        return rec
+
+    def finish(rec):
+        """Closes the process group and prints the ONE JSON line on rank 0 (exit 3 on a parity failure)."""
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            import ctypes
+            try:
+                ctypes.CDLL(None).fflush(None)      # native stdio buffers go where fd 1 points now (stderr)
+            except Exception:  # noqa: BLE001
+                pass
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(rec) + "\n").encode())
+            if "parity" in rec and not rec["parity"]["ok"]:
+                sys.stderr.write(f"bench.py: PARITY FAILURE: max rel err {rec['parity']['max_rel_err']:.3e} > 1e-4 against the oracle\n")
+                raise SystemExit(3)
+
+    if not args.full:
+        # a plain run: the headline figure and nothing else (the device status word of the timed launches is still read: an
+        # error the kernels flagged fails the run)
+        ops.check_status(dev)
+        ranks_seen = 1
+        if use_dist:
+            ones = torch.ones(1, dtype=torch.int64, device=dev)
+            dist.all_reduce(ones, op=dist.ReduceOp.SUM)       # every rank that took part in the timed region counts itself
+            ranks_seen = int(ones.item())
+        checksum = float(outs[primary.last_out].sum().item())
+        assert checksum == checksum and checksum > 0, "bench produced non-finite distances"
+        finish(headline_record(ranks_seen) if rank == 0 else None)
+        return
+
+    timed_out0 = outs[0].clone()            # what the TIMED launches wrote for batch 0: the parity object checks this copy
     # the same K steps once more, untimed by the wall clock, bracketed by HIP events on the launch stream: what the GPU
     # side of such a region takes (recording events INSIDE the wall-timed region costs it ~70 us of host time)
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -806,37 +920,13 @@ def main():
                     "frac_of_measured_copy_bw": ach / MEASURED_COPY_GBS,
                     "mode": note}
 
-        rec = {
-            "metric": "pairwise Siegel distances/sec (upper, riem, n=4)" if args.workload == "upper-riem-n4-b65536"
-                      else (f"pairwise SPD affine-invariant distances/sec (n={n})" if model == "spd"
-                            else f"pairwise Siegel distances/sec ({model}, {metric}, n={n})"),
-            "value": value, "unit": "pairs/s", "n_gpus": world, "ranks_seen": ranks_seen,
-            "steps": args.steps, "warmup": args.warmup,
-            # the MEDIAN of `repetitions` repetitions of the K-step timed region (each: barrier + synchronize, exactly K steps,
-            # synchronize; max over ranks per repetition); the spread and the first repetition are beside it
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "ms_per_step_min": t_primary["min"] / args.steps * 1e3, "ms_per_step_max": t_primary["max"] / args.steps * 1e3,
-            "ms_per_step_first": t_primary["first"] / args.steps * 1e3,
-            "ms_per_step_all": [x / args.steps * 1e3 for x in t_primary["all"]], "repetitions": len(t_primary["all"]),
-            # fastest and slowest rank of the median repetition (K steps, milliseconds)
-            "elapsed_ranks_ms": {"min": t_primary["rank_min_of_median"] * 1e3, "max": t_primary["rank_max_of_median"] * 1e3},
+        rec = headline_record(ranks_seen)
+        rec.update({
             # HIP events on the launch stream around an identical repetition of the K steps (max over ranks): what the GPU
             # side of the timed region takes, launch latency of the first graph included
             "ms_per_step_device": device_ms / args.steps,
             # wall-clock-free throughput of the same region (the ~10 us of launch + sync latency of a K = 20 region excluded)
             "value_device": global_pairs * args.steps / (device_ms * 1e-3),
-            "launch_mode": args.launch, "steps_per_launch": (min(spl, args.steps) if fused is not None else 1),
-            "higher_is_better": True, "scaling": args.scaling,
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": args.workload, "manifold": model, "dist_metric": metric,
-                       "dims": n, "nodes": nodes, "pairs_per_gpu_per_step": my_pairs,
-                       "global_pairs_per_step": global_pairs, "table": args.table, "pairs": args.pairs,
-                       "launch": args.launch,
-                       "api": ("Model.forward_batches(Model.prepare_batches(list of K batches))" if (fused is not None and
-                                                                                spl == ops.MAX_FUSED_BATCHES)
-                               else "ops (C-ABI binding) directly"),
-                       "streams": args.streams,
-                       "parallelism": f"pairs sharded rank::{world}, table replicated, no collective"},
             # the kernel the timed region ran, its launches strictly sequential (what rocprofv3 --kernel-trace reports)
             "roofline": roof(timed_kernel, k_timed, timed_pairs_per_launch,
                              ("the timed region's kernel: one launch evaluates up to %d consecutive steps (batches); duration = "
@@ -850,8 +940,7 @@ def main():
                              "limiter is fp64 VALU issue: see valu_issue_fraction and DESIGN.md section 5"),
             # whole-job throughput of the timed region expressed against the same roof
             "throughput_frac_of_hbm_roof": (value / world) * bpp / (HBM_PEAK_GBS * 1e9),
-        }
-        rec["config"]["steps_per_launch"] = min(spl, args.steps) if fused is not None else 1
+        })
         if pack_us is not None:
             rec["packed_table"] = {"pack_us": pack_us, "rows": nodes,
                                    "ms_per_step_if_the_table_changed_before_every_step": rec["ms_per_step"] + pack_us * 1e-3,
@@ -860,8 +949,6 @@ def main():
                                            "sympa_table_pack / sympa_spd_table_pack); the pack is NOT in the "
                                            "timed region (the table does not change between the K steps, as in Runner.evaluate, "
                                            "runner.py:124-135) -- its cost is reported here"}
-        rec["value_" + args.scaling] = value
-        rec["ms_per_step_" + args.scaling] = rec["ms_per_step"]
         if t_other is not None:
             o = other.scaling
             rec["value_" + o] = other.global_pairs * args.steps / t_other["elapsed"]
@@ -952,20 +1039,7 @@ def main():
             if bad_rows:
                 sys.stderr.write("bench.py: secondary rows with a parity failure: " + ", ".join(
                     f"{r['workload']}/{r['kind']}/{r.get('form', '')}" for r in bad_rows) + "\n")
-    if use_dist:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        import ctypes
-        try:
-            ctypes.CDLL(None).fflush(None)      # native stdio buffers go where fd 1 points now (stderr)
-        except Exception:  # noqa: BLE001
-            pass
-        sys.stdout.flush()
-        os.write(json_fd, (json.dumps(rec) + "\n").encode())
-        if not rec["parity"]["ok"]:
-            sys.stderr.write(f"bench.py: PARITY FAILURE: max rel err {rec['parity']['max_rel_err']:.3e} > 1e-4 against the oracle\n")
-            raise SystemExit(3)
+    finish(rec if rank == 0 else None)
 
 
 if __name__ == "__main__":

@@ -47,7 +47,7 @@ def test_bench_two_ranks_on_one_gpu_shard_rank_by_rank_and_merge_to_the_single_p
     from sympa_amd import data, ops
     dump = str(tmp_path / "dump")
     args = ["--gpus", "2", "--steps", "6", "--warmup", "2", "--batch", "8192", "--scaling", "strong", "--distinct-batches", "3",
-            "--no-cpu-baseline", "--no-live-traffic"]
+            "--full", "--no-cpu-baseline", "--no-live-traffic"]
     proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                           env=_env(SYMPA_BENCH_BACKEND="gloo", SYMPA_BENCH_SHARE_GPU="1", SYMPA_BENCH_DUMP=dump), timeout=600,
                           cwd=ROOT)
@@ -212,7 +212,7 @@ def test_bench_eight_ranks_on_one_gpu_strong_scaling_merges_to_the_single_proces
     from sympa_amd import data, ops
     dump = str(tmp_path / "dump")
     args = ["--gpus", "8", "--steps", "6", "--warmup", "2", "--scaling", "strong", "--distinct-batches", "3", "--repeats", "3",
-            "--no-cpu-baseline", "--no-live-traffic"]
+            "--full", "--no-cpu-baseline", "--no-live-traffic"]
     proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                           env=_env(SYMPA_BENCH_BACKEND="gloo", SYMPA_BENCH_SHARE_GPU="1", SYMPA_BENCH_DUMP=dump), timeout=1200,
                           cwd=ROOT)

@@ -24,12 +24,12 @@ for x in f: print('  FALLBACK', x)
 sys.exit(1 if f else 0)" 2>&1 | grep -v amdgpu.ids | tee -a $OUT/selfcheck.txt
 [ ${PIPESTATUS[0]} -eq 0 ] || FAIL=1
 echo "== bench (driver's command line, then defaults)"
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 2>$OUT/bench_k20.err | tail -1 | tee $OUT/bench_k20.json | cut -c1-300
-timeout 600 python bench.py 2>$OUT/bench.err | tail -1 | tee $OUT/bench.json | cut -c1-300
-SYMPA_BENCH_FORCE_DIST=1 timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-live-traffic 2>$OUT/bench_k20_dist.err | tail -1 | tee $OUT/bench_k20_forcedist.json | cut -c1-200
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 2>$OUT/bench_k20.err | tail -1 | tee $OUT/bench_k20.json | cut -c1-300
+timeout 600 python bench.py --full 2>$OUT/bench.err | tail -1 | tee $OUT/bench.json | cut -c1-300
+SYMPA_BENCH_FORCE_DIST=1 timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-live-traffic 2>$OUT/bench_k20_dist.err | tail -1 | tee $OUT/bench_k20_forcedist.json | cut -c1-200
 echo "== rocprof kernel trace (same commands)"
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_k20 -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-live-traffic > $OUT/prof_k20.log 2>&1
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 bench.py --no-cpu-baseline --no-live-traffic > $OUT/prof_bench.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_k20 -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-live-traffic > $OUT/prof_k20.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 bench.py --full --no-cpu-baseline --no-live-traffic > $OUT/prof_bench.log 2>&1
 for d in prof_k20 prof; do find $OUT/$d -name "*kernel_stats.csv" | head -1 | xargs -r head -4; done | tee $OUT/kernel_stats_head.txt
 bash tools/pmc_collect.sh $TAG > $OUT/pmc.log 2>&1
 tail -30 $OUT/pmc.log
@@ -37,15 +37,15 @@ bash tools/pmc_collect.sh ${TAG}_single upper-riem-n4-b65536 "siegel_dist_kernel
 tail -30 $OUT/pmc_single.log
 echo "== secondary workloads (bench line, then rocprof kernel trace of each, one launch per step and sequential: clean per-kernel figures)"
 for W in margulis-bounded-finf-n4-b65536 cartesian-upper-riem-n8-b262144 custom-spd-n16-b1048576 tree-upper-riem-n4-b8192 grid-upper-riem-n2-b512; do
-  timeout 600 python bench.py --workload $W --steps 64 --warmup 8 2>$OUT/bench_$W.err | tail -1 > $OUT/bench_$W.json
+  timeout 600 python bench.py --full --workload $W --steps 64 --warmup 8 2>$OUT/bench_$W.err | tail -1 > $OUT/bench_$W.json
   cut -c1-300 $OUT/bench_$W.json
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$W -- python3 bench.py --workload $W --no-cpu-baseline --no-live-traffic --steps 64 --warmup 8 --launch graph --streams 1 > $OUT/prof_$W.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$W -- python3 bench.py --full --workload $W --no-cpu-baseline --no-live-traffic --steps 64 --warmup 8 --launch graph --streams 1 > $OUT/prof_$W.log 2>&1
   find $OUT/prof_$W -name "*kernel_stats.csv" | head -1 | xargs -r head -2
 done
 echo "== the graph workloads on their real (i < j, d) triplets (--pairs graph: evaluation order; graph-shuffled: training order)"
 for W in grid-upper-riem-n2-b512 tree-upper-riem-n4-b8192 margulis-bounded-finf-n4-b65536; do
   for P in graph graph-shuffled; do
-    timeout 600 python bench.py --workload $W --pairs $P --steps 64 --warmup 8 --no-cpu-baseline --no-live-traffic 2>>$OUT/bench_graph.err | tail -1 | tee -a $OUT/bench_graph_pairs.json | cut -c1-200
+    timeout 600 python bench.py --full --workload $W --pairs $P --steps 64 --warmup 8 --no-cpu-baseline --no-live-traffic 2>>$OUT/bench_graph.err | tail -1 | tee -a $OUT/bench_graph_pairs.json | cut -c1-200
   done
 done
 echo "== evaluation epoch of the harness (Model.evaluate on configs[1]'s 596 778 triplets, batch 8192)"
@@ -67,7 +67,7 @@ WORKLOADS=headline timeout 600 rocprofv3 --kernel-trace --stats --output-format 
 find $OUT/prof_train -name "*kernel_stats.csv" | head -1 | xargs -r head -12 | tee $OUT/train_kernel_stats_head.txt
 echo "== round 4: per-call host cost of the two bindings, --launch direct, the replayed multi-GPU step at world size 1 over RCCL"
 timeout 300 python3 tools/host_call_time.py 2>&1 | grep -v amdgpu.ids | tee $OUT/host_call.txt
-timeout 300 python bench.py --launch direct --steps 2000 --warmup 200 --no-cpu-baseline --no-live-traffic 2>$OUT/bench_direct.err | tail -1 | tee $OUT/bench_direct.json | cut -c1-260
+timeout 300 python bench.py --full --launch direct --steps 2000 --warmup 200 --no-cpu-baseline --no-live-traffic 2>$OUT/bench_direct.err | tail -1 | tee $OUT/bench_direct.json | cut -c1-260
 timeout 600 python3 tools/dist_step_time.py 24 2>&1 | grep "us/step" | tee $OUT/dist_step.txt
 echo "== round 4: spd n = 16 backward, three kernels (eigenvectors one pair per lane) against the QL-with-vectors kernel"
 { timeout 600 python3 tools/spd_bwd3_ab.py 1048576 2>&1 | grep -v amdgpu.ids | tail -2; timeout 300 python3 tools/spd_bwd3_ab.py 65536 2>&1 | grep -v amdgpu.ids | tail -2; } | tee $OUT/spd_bwd3_ab.txt
