@@ -647,31 +647,39 @@ SYMPA_UNROLL
 // golden, the 50-digit values and the graded-spectrum forward tests are unchanged or closer (profiles/r06_ql_deflation.txt).
 // FORWARD only (eigenvalues are all that leaves): the iterations that accumulate or feed eigenVECTORS (backward: tridiag_ql_vectors,
 // the inverse-iteration routes) keep eps^2 -- a vector sees a neglected off-diagonal in FIRST order, e / gap.
+// The metrics that weight the eigenvalues of a cluster unequally (finf, fmin, wsum) and a caller that asks for v itself see the
+// SECOND-order shift of each eigenvalue: measured 1.2e-11 of max v at a relative gap of 1e-10 (tests/test_exact_reference.py,
+// 50-digit values), 3 orders above rounding.  Those pass QL_DEFLATE_TOL_EXACT (dsterf's eps^2) as `tol` at run time
+// (ql_deflate_tol_for); riem and fone, symmetric in a cluster, keep 1e-20.
 constexpr double QL_DEFLATE_TOL = 1e-20;
+constexpr double QL_DEFLATE_TOL_EXACT = 1.3e-32;
 SYMPA_HD bool ql_negligible(double e2, double da, double db) { return !(e2 > 1.3e-32 * fabs(da * db) + 1e-290); }
 template <bool VALUES_ONLY>
-SYMPA_HD bool ql_deflated(double e2, double da, double db) {
-    return !(e2 > (VALUES_ONLY ? QL_DEFLATE_TOL : 1.3e-32) * fabs(da * db) + 1e-290);
+SYMPA_HD bool ql_deflated(double e2, double da, double db, double tol = QL_DEFLATE_TOL) {
+    return !(e2 > (VALUES_ONLY ? tol : 1.3e-32) * fabs(da * db) + 1e-290);
+}
+SYMPA_HD double ql_deflate_tol_for(int metric, bool wants_vvd) {
+    return (metric == METRIC_RIEM || metric == METRIC_FONE) && !wants_vvd ? QL_DEFLATE_TOL : QL_DEFLATE_TOL_EXACT;
 }
 
 template <int N, int L, bool VALUES_ONLY>
-SYMPA_HD bool tridiag_ql_stage(double (&d)[N], double (&e2)[N]) {
+SYMPA_HD bool tridiag_ql_stage(double (&d)[N], double (&e2)[N], const double tol) {
     bool conv = false;
     for (int it = 0; it < 60; ++it) {
-        conv = ql_deflated<VALUES_ONLY>(e2[L], d[L], d[L + 1]);
+        conv = ql_deflated<VALUES_ONLY>(e2[L], d[L], d[L + 1], tol);
         if (wave_all(conv)) break;
         double dl = d[L], dl1 = d[L + 1], el = e2[L];
         bool idle = conv;
         e2[L] = conv ? 0.0 : e2[L];
         if constexpr (L + 1 <= N - 2) {
-            const bool c1 = ql_deflated<VALUES_ONLY>(e2[L + 1], d[L + 1], d[L + 2]);
+            const bool c1 = ql_deflated<VALUES_ONLY>(e2[L + 1], d[L + 1], d[L + 2], tol);
             dl = idle ? d[L + 1] : dl;
             dl1 = idle ? d[L + 2] : dl1;
             el = idle ? e2[L + 1] : el;
             idle = idle && c1;
             e2[L + 1] = idle ? 0.0 : e2[L + 1];
             if constexpr (L + 2 <= N - 2) {
-                const bool c2 = ql_deflated<VALUES_ONLY>(e2[L + 2], d[L + 2], d[L + 3]);
+                const bool c2 = ql_deflated<VALUES_ONLY>(e2[L + 2], d[L + 2], d[L + 3], tol);
                 dl = idle ? d[L + 2] : dl;
                 dl1 = idle ? d[L + 3] : dl1;
                 el = idle ? e2[L + 2] : el;
@@ -716,13 +724,14 @@ SYMPA_UNROLL
 
 // VALUES_ONLY = true: the forward's eigenvalues (deflation at QL_DEFLATE_TOL); false (default): eps^2, for callers whose
 // eigenvalues feed eigenvectors or spectral weights of a backward
+// (tol: the VALUES_ONLY deflation threshold, QL_DEFLATE_TOL or QL_DEFLATE_TOL_EXACT)
 template <int N, int L = 0, bool VALUES_ONLY = false>
-SYMPA_HD bool tridiag_ql_lockstep(double (&d)[N], double (&e2)[N]) {
+SYMPA_HD bool tridiag_ql_lockstep(double (&d)[N], double (&e2)[N], const double tol = QL_DEFLATE_TOL) {
     if constexpr (L >= N - 1) {
         return true;
     } else {
-        const bool here = tridiag_ql_stage<N, L, VALUES_ONLY>(d, e2);
-        const bool rest = tridiag_ql_lockstep<N, L + 1, VALUES_ONLY>(d, e2);
+        const bool here = tridiag_ql_stage<N, L, VALUES_ONLY>(d, e2, tol);
+        const bool rest = tridiag_ql_lockstep<N, L + 1, VALUES_ONLY>(d, e2, tol);
         return here && rest;
     }
 }
@@ -730,14 +739,15 @@ SYMPA_HD bool tridiag_ql_lockstep(double (&d)[N], double (&e2)[N]) {
 // Eigenvalues of H into h.d[]: Jacobi for n <= 4, tridiagonal QL for n >= 5.
 // (n = 4 through Householder + lockstep QL instead of Jacobi was measured in round 5, profiles/r05_n4_eigen_ab.txt: 9.10 -> 10.19 us
 // per 65 536 pairs, the fused 20-step launch 88.0 -> 96.8 us, and the `far` golden fails at 1e-6: Jacobi stays.)
+// (ql_tol: the QL's deflation threshold, ql_deflate_tol_for; Jacobi's certificate is relative to the gaps already)
 template <int N>
-SYMPA_HD bool herm_eigenvalues(Herm<N>& h) {
+SYMPA_HD bool herm_eigenvalues(Herm<N>& h, const double ql_tol = QL_DEFLATE_TOL) {
     if constexpr (N <= 4) {
         return herm_eigenvalues_jacobi<N>(h);
     } else {
         double a[N], b2[N];
         herm_tridiagonalize<N>(h, a, b2);
-        const bool ok = tridiag_ql_lockstep<N, 0, true>(a, b2);
+        const bool ok = tridiag_ql_lockstep<N, 0, true>(a, b2, ql_tol);
 SYMPA_UNROLL
         for (int i = 0; i < N; ++i) h.d[i] = a[i];
         return ok;
@@ -818,7 +828,7 @@ SYMPA_UNROLL
 template <int N, int MODEL>
 SYMPA_HD double distance_from_h(Herm<N>& h, const bool ok, int metric, const double* __restrict__ w,
                                 double inv_eps, double* __restrict__ vvd, int& status) {
-    const bool conv = herm_eigenvalues<N>(h);
+    const bool conv = herm_eigenvalues<N>(h, ql_deflate_tol_for(metric, vvd != nullptr));
 
     const double scale = (MODEL == MODEL_UPPER) ? 0.25 : 1.0;
     double v[N];

@@ -71,7 +71,10 @@ SYMPA_UNROLL
     }
 }
 
-constexpr double JACOBI_VEC_TOL2 = 1e-22;
+// ||off|| <= 1e-14 ||diag||.  The eigenvectors see the off-diagonal in FIRST order (off / gap): at 1e-22 (1e-11 ||diag||) the
+// n <= 4 gradients were 5e-12 off at generic pairs and 1e-6 off for finf / fmin / wsum at a relative gap of 1e-7, against the
+// 50-digit directional derivatives of tests/test_exact_reference.py; at 1e-28 they sit at the other routes' rounding level.
+constexpr double JACOBI_VEC_TOL2 = 1e-28;
 
 template <int N>
 SYMPA_HD bool herm_eigen_vectors(Herm<N>& h, CMat<N>& v) {

@@ -117,7 +117,9 @@ SYMPA_HD double pair_distance_generic(GenericWork& w, const double* __restrict__
             w.hr[gix(n, j, k)] = tr; w.hi[gix(n, j, k)] = (j == k) ? 0.0 : ti;
             w.hr[gix(n, k, j)] = tr; w.hi[gix(n, k, j)] = (j == k) ? 0.0 : -ti;
         }
-    // cyclic Jacobi on the full Hermitian matrix until ||off|| <= 1e-11 ||diag||
+    // cyclic Jacobi on the full Hermitian matrix until ||off|| <= 1e-14 ||diag||.  (At 1e-11 the small eigenvalues of a graded H kept
+    // off^2 / lambda: v 4e-7 of max v off at a singular-value spread of 1e-6 against the 50-digit values of
+    // tests/test_exact_reference.py; the off-diagonal shrinks with the entries it mixes, so the tighter test costs a sweep, not a floor.)
     bool conv = (n == 1);
     for (int sweep = 0; sweep < 30 && n > 1; ++sweep) {
         double off2 = 0.0, diag2 = 0.0;
@@ -125,7 +127,7 @@ SYMPA_HD double pair_distance_generic(GenericWork& w, const double* __restrict__
             diag2 += w.hr[gix(n, j, j)] * w.hr[gix(n, j, j)];
             for (int k = j + 1; k < n; ++k) off2 += w.hr[gix(n, j, k)] * w.hr[gix(n, j, k)] + w.hi[gix(n, j, k)] * w.hi[gix(n, j, k)];
         }
-        conv = !(off2 > 1e-22 * diag2);
+        conv = !(off2 > 1e-28 * diag2);
         if (wave_all(conv)) break;
         for (int p = 0; p < n - 1; ++p)
             for (int q = p + 1; q < n; ++q) {
