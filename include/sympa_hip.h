@@ -514,6 +514,33 @@ int sympa_spd_projx(const double* x, int64_t b, int n, double* out, int32_t* pro
 int sympa_spd_rsgd_step(double* table, const double* grad, int64_t num_rows, int n, double lr, double weight_decay,
                         const double* total_sqnorm, double max_norm, int32_t* status, void* stream);
 
+/* Per-row average precision of a block of rows of the all-pairs distance matrix: the ranking half of
+ * MeanAveragePrecisionMetric.calculate_metric (sympa/metrics.py:39-63) over the matrix Runner.calculate_mAP builds
+ * (sympa/runner.py:137-154), without sorting the rows (csrc/map_rank.hip).
+ *   dist        [row_count, ld] fp64: rows row_begin .. row_begin + row_count - 1 of the N x N matrix (N = num_rows), row i
+ *               holding d(i, k) with i the source (sympa_all_pairs_dist / sympa_all_pairs_dist_packed with
+ *               SYMPA_FLAG_NO_SYMMETRY); 8-byte aligned, ld >= num_rows
+ *   rowptr      [num_rows + 1] int64, cols [rowptr[num_rows]] int32: neighbour lists (CSR, each row sorted and unique) of the
+ *               rule metrics.py:33-37 applies (graph distance == 1, both directions); an entry equal to its own row is ignored
+ *   max_degree  largest rowptr[i + 1] - rowptr[i]: rows above SYMPA_MAP_LDS_CAP entries need
+ *               sympa_map_workspace_bytes(num_rows, max_degree) bytes of caller-owned, 16-byte aligned device `workspace`
+ *               (returns 0 when none is needed)
+ *   ap          [row_count] fp64, written: ap[r] = mean_t(t / r_t) over the neighbours t = 1..deg of row row_begin + r in key
+ *               order, r_t their 1-based positions among the columns other than self; NaN for a row without neighbours
+ *               (np.mean([]), metrics.py:61)
+ *   flags       0 or SYMPA_FLAG_FP32_KEYS: every distance is rounded to fp32 before it is compared (the reference's
+ *               float32 torch.zeros matrix, runner.py:144)
+ * Order of a row: self first, the other columns k by the key (d[k], k): ascending distance, ties by column index (a stable
+ * argsort; the reference's np.argsort is unstable, so its order of exactly tied entries is arbitrary), -0 counts as +0, NaN
+ * after every number.  CSR entries outside [0, num_rows), or a row longer than max_degree, set SYMPA_ST_BAD_INDEX in `status`
+ * and that row's ap to NaN. */
+#define SYMPA_FLAG_FP32_KEYS 256
+#define SYMPA_MAP_LDS_CAP 1024
+int64_t sympa_map_workspace_bytes(int64_t num_rows, int64_t max_degree);
+int sympa_map_rows(const double* dist, int64_t row_count, int64_t ld, int64_t row_begin, int64_t num_rows,
+                   const int64_t* rowptr, const int32_t* cols, int64_t max_degree, double* ap, void* workspace,
+                   int64_t workspace_bytes, int32_t* status, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

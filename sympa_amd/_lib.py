@@ -65,6 +65,8 @@ SYMBOLS = (
     "sympa_spd_egrad2rgrad",
     "sympa_spd_projx",
     "sympa_spd_rsgd_step",
+    "sympa_map_workspace_bytes",
+    "sympa_map_rows",
 )
 
 _c_double_p = ctypes.c_void_p
@@ -302,6 +304,11 @@ def load():
     lib.sympa_spd_model_forward_packed.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, _c_i64_p, C.c_int64, _c_i64_p,
                                                    C.c_int64, C.c_int64, _c_double_p, C.c_double, _c_double_p, _c_i32_p, C.c_int,
                                                    C.c_void_p]
+    lib.sympa_map_workspace_bytes.restype = C.c_int64
+    lib.sympa_map_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+    lib.sympa_map_rows.restype = C.c_int
+    lib.sympa_map_rows.argtypes = [_c_double_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _c_i64_p, _c_i32_p, C.c_int64,
+                                   _c_double_p, C.c_void_p, C.c_int64, _c_i32_p, C.c_int, C.c_void_p]
     _lib = lib
     return lib
 

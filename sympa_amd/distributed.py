@@ -281,6 +281,26 @@ def allreduce_scalar(t, group=None, op="sum"):
     return t
 
 
+def row_shard(num_rows, group=None):
+    """(first row, row count) of this rank's contiguous share of `num_rows` rows: ceil(num_rows / world) rows per rank, the
+    last ranks' shares shorter or empty; (0, num_rows) without an initialised process group."""
+    if not (dist.is_available() and dist.is_initialized()):
+        return 0, int(num_rows)
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    per = -(-int(num_rows) // world)
+    begin = min(rank * per, int(num_rows))
+    return begin, min(per, int(num_rows) - begin)
+
+
+def allreduce_row_shards(t, group=None):
+    """Assembles a per-row vector whose ranks each wrote their own rows (row_shard) into a zero-filled tensor: a SUM all-reduce, exact
+    because every entry is x + 0 + ... + 0 (NaN stays NaN), so the result is bitwise what one process computes (Model.mean_average_
+    precision's [N] AP vector)."""
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t
+
+
 def shard_triplets(triplets, rank, world, epoch=0, seed=0, shuffle=True):
     """This rank's share of a triplet tensor, exactly what DataLoader(sampler=DistributedSampler(...))
     iterates over in train.py:105-110."""

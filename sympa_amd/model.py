@@ -332,6 +332,58 @@ class Model(nn.Module):
         return ops.all_pairs_dist(self.embeddings.embeds, man.model_name, man.metric.kind.value, weights, self.scale,
                                   self.scale_coef, row_begin, row_count)
 
+    def mean_average_precision(self, triples_or_metric, dtype=torch.float32, max_block_bytes=128 << 20, group=None,
+                               return_rows=False):
+        """Extension: Runner.calculate_mAP (runner.py:137-140) on the device, never holding more than a bounded slab of the matrix.
+        Rows are produced a block at a time into ONE reused [R, N] buffer (R from max_block_bytes) by the row-oriented all-pairs
+        kernels (packed kernel for upper / bounded dims <= 8, pairwise kernels for dims 9..16; spd: distance_matrix(row_begin,
+        row_count), whose [R * N, 2] pair list is counted against the budget) and each block is ranked by ops.map_rows.
+        `triples_or_metric`: a sympa_amd.metrics.MeanAveragePrecisionMetric, or what its constructor takes.  dtype=torch.float32
+        compares fp32-rounded distances, like the reference's float32 matrix (runner.py:144); torch.float64 the fp64 values.
+        With `group` set or a default process group initialised, every rank ranks its own contiguous share of the rows and the
+        [N] AP vector is assembled by an exact all-reduce of zero-padded vectors, so the result does not depend on the world size
+        or on the block size.  Reads the table only: forward caches and the packed-table state are untouched.  One host sync
+        (the returned float); with return_rows=True returns (mAP, AP [N] fp64 device tensor)."""
+        from sympa_amd import distributed as sd
+        from sympa_amd import metrics as sm
+        if dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"dtype must be torch.float32 or torch.float64, got {dtype}")
+        man = self.manifold
+        table = self.embeddings.embeds.detach()
+        dev = table.device
+        ops._need_gpu(table, "embedding table")
+        N = table.shape[0]
+        metric = triples_or_metric if isinstance(triples_or_metric, sm.MeanAveragePrecisionMetric) else \
+            sm.MeanAveragePrecisionMetric(triples_or_metric)
+        nbrs = metric.csr(N, dev)
+        spd = man.model_name == "spd"
+        row_bytes = (8 + 16 + 16) * N if spd else 8 * N       # spd: output + [N, 2] pair list + the arange repeats behind it
+        R = max(1, int(max_block_bytes) // row_bytes)
+        begin, count = (0, N) if group is None and not sd.dist.is_initialized() else sd.row_shard(N, group)
+        R = min(R, max(count, 1))
+        ap = torch.zeros(N, dtype=torch.float64, device=dev)
+        float32 = dtype == torch.float32
+        if not spd:
+            weights = man.metric.weights if man.metric.kind is MetricType.WEIGHTED_SUM else None
+            n = table.shape[-1]
+            need = ops._lib.load().sympa_all_pairs_workspace_bytes(N, n, ops.MODEL_IDS[man.model_name])
+            ws = torch.empty(need // 8, dtype=torch.float64, device=dev) if need > 0 else None
+            buf = torch.empty(R, N, dtype=torch.float64, device=dev) if count > 0 else None
+        with torch.no_grad():
+            for b in range(begin, begin + count, R):
+                r = min(R, begin + count - b)
+                if spd:
+                    rows = self.distance_matrix(b, r)
+                else:
+                    rows = ops.all_pairs_dist(table, man.model_name, man.metric.kind.value, weights, self.scale.detach(),
+                                              self.scale_coef, b, r, out=buf[:r], packed=need > 0, workspace=ws,
+                                              flags=ops.FLAG_NO_SYMMETRY)
+                ops.map_rows(rows, b, nbrs, float32=float32, out=ap[b:b + r], max_degree=metric.max_degree)
+        if group is not None or sd.dist.is_initialized():
+            sd.allreduce_row_shards(ap, group)
+        value = float(ap.mean())
+        return (value, ap) if return_rows else value
+
     def distance(self, src_embeds, dst_embeds):   # model.py:32-38
         return self.manifold.dist(src_embeds, dst_embeds)
 

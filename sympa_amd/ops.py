@@ -1490,3 +1490,86 @@ def spd_rsgd_step_(table, grad, lr, weight_decay=0.0, clip_sqnorm=None, max_norm
                                      float(max_norm) if max_norm is not None else 0.0, st.data_ptr(), _stream())
     _lib.check(rc)
     return table
+
+
+# ---------------------------------------------------------------------------------------------------
+# Mean average precision (C-ABI sympa_map_rows; reference sympa/metrics.py:25-63, runner.py:137-154)
+# ---------------------------------------------------------------------------------------------------
+FLAG_FP32_KEYS = 256   # map_rows: round every distance to fp32 before comparing (the reference's float32 matrix)
+MAP_LDS_CAP = 1024     # map_rows: rows with more CSR entries take the workspace kernel (SYMPA_MAP_LDS_CAP)
+
+
+def neighbor_csr(src_dst_ids, graph_distances, num_nodes):
+    """Neighbour lists of MeanAveragePrecisionMetric.__init__ (metrics.py:30-37) as a CSR on the ids' device, with torch ops only:
+    j is a neighbour of i when some triple (i, j, g) or (j, i, g) has g == 1 exactly (compared in the distance tensor's own dtype,
+    as the reference's `distance == 1` compares the tensor's value); duplicates collapse.  Returns (rowptr int64 [num_nodes + 1],
+    cols int32 [E]), each row's columns ascending.  Raises IndexError when an id is outside [0, num_nodes)."""
+    ids = torch.as_tensor(src_dst_ids)
+    if ids.dim() != 2 or ids.shape[1] < 2:
+        raise ValueError(f"src_dst_ids must be [T, >=2], got {tuple(ids.shape)}")
+    ids = ids[:, :2].to(torch.int64)
+    gd = torch.as_tensor(graph_distances, device=ids.device).reshape(-1)
+    if gd.numel() != ids.shape[0]:
+        raise ValueError(f"{ids.shape[0]} triples but {gd.numel()} graph distances")
+    num_nodes = int(num_nodes)
+    if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= num_nodes):
+        raise IndexError(f"a node id is outside [0, {num_nodes})")
+    mask = gd == 1
+    src, dst = ids[mask, 0], ids[mask, 1]
+    key = torch.unique(torch.cat((src * num_nodes + dst, dst * num_nodes + src)))      # sorted: by row, then column
+    rows = key // num_nodes
+    cols = (key - rows * num_nodes).to(torch.int32)
+    rowptr = torch.zeros(num_nodes + 1, dtype=torch.int64, device=ids.device)
+    rowptr[1:] = torch.cumsum(torch.bincount(rows, minlength=num_nodes), 0)
+    return rowptr, cols
+
+
+def map_workspace_bytes(num_rows, max_degree):
+    return int(_lib.load().sympa_map_workspace_bytes(int(num_rows), int(max_degree)))
+
+
+def map_rows(dist_rows, row_begin, neighbors, float32=False, out=None, workspace=None, max_degree=None):
+    """Per-row average precision of rows [row_begin, row_begin + R) of the N x N distance matrix (C-ABI sympa_map_rows) on the
+    current stream.  dist_rows: fp64 [R, N] device tensor (unit column stride) holding d(i, k) with row point i the source
+    (all_pairs_dist(..., flags=FLAG_NO_SYMMETRY) or Model.distance_matrix(row_begin, R)); neighbors: (rowptr, cols) of
+    neighbor_csr on the same device; float32=True rounds every distance to fp32 before it is compared (the reference's
+    float32 matrix, runner.py:144).  Returns out [R] fp64: ties are broken by column index (a stable sort), so rows with
+    exactly tied distances can differ from the reference's unstable np.argsort; NaN for a row without neighbours.
+    max_degree (largest CSR row) is read from the device when not given (one host sync)."""
+    lib = _lib.load()
+    _need_gpu(dist_rows, "dist_rows")
+    if dist_rows.dtype != torch.float64 or dist_rows.dim() != 2 or (dist_rows.shape[0] > 1 and dist_rows.stride(1) != 1):
+        raise ValueError(f"dist_rows must be a float64 [R, N] tensor with unit column stride, got {dist_rows.dtype} "
+                         f"{tuple(dist_rows.shape)}")
+    if dist_rows.stride(1) != 1:
+        dist_rows = dist_rows.contiguous()
+    rowptr, cols = neighbors[0], neighbors[1]
+    R, N = dist_rows.shape
+    dev = dist_rows.device
+    if rowptr.device != dev or cols.device != dev or rowptr.dtype != torch.int64 or cols.dtype != torch.int32:
+        raise ValueError("neighbors must be (int64 rowptr, int32 cols) on the rows' device")
+    if rowptr.numel() != N + 1:
+        raise ValueError(f"rowptr has {rowptr.numel()} entries for a matrix of {N} columns (want {N + 1})")
+    rowptr, cols = rowptr.contiguous(), cols.contiguous()
+    if max_degree is None:
+        max_degree = int((rowptr[1:] - rowptr[:-1]).max()) if N else 0
+    if out is None:
+        out = torch.empty(R, dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or out.device != dev or out.numel() != R or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float64 [R] tensor on the rows' device")
+    need = lib.sympa_map_workspace_bytes(N, int(max_degree))
+    if need > 0:
+        if workspace is None or workspace.numel() * workspace.element_size() < need:
+            workspace = torch.empty((need + 15) // 16, 2, dtype=torch.float64, device=dev)
+    ld = dist_rows.stride(0) if R > 1 else N
+    st = _status_buf(dev)
+    with torch.cuda.device(dev):
+        rc = lib.sympa_map_rows(dist_rows.data_ptr(), R, ld, int(row_begin), N, rowptr.data_ptr(),
+                                cols.data_ptr() if cols.numel() else None, int(max_degree), out.data_ptr(),
+                                workspace.data_ptr() if need > 0 else None,
+                                workspace.numel() * workspace.element_size() if need > 0 else 0, st.data_ptr(),
+                                FLAG_FP32_KEYS if float32 else 0, _stream())
+    _lib.check(rc)
+    if _debug:
+        check_status(dev)
+    return out
