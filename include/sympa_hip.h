@@ -31,6 +31,12 @@ extern "C" {
 /* models: ManifoldFactory.sympa_manifolds keys (sympa/embeddings.py:145-149) */
 #define SYMPA_MODEL_UPPER 0   /* UpperHalfManifold   sympa/manifolds/upper_half.py:8 */
 #define SYMPA_MODEL_BOUNDED 1 /* BoundedDomainManifold sympa/manifolds/bounded_domain.py:10 */
+#define SYMPA_MODEL_DUAL 2    /* CompactDualManifold sympa/manifolds/compact_dual.py:8.  One pair (row) per lane and runtime-n kernels only:
+                                 SYMPA_FLAG_COOP / SYMPA_FLAG_SPLIT are ignored, sympa_table_pack_bytes returns 0 (no packed path),
+                                 sympa_table_pack* / sympa_model_forward*_packed / sympa_tangent_sqnorm / sympa_radam_step* /
+                                 sympa_rsgd_step_fused return SYMPA_ERR_BAD_ARG (the reference's inner raises NotImplementedError,
+                                 compact_dual.py:96), sympa_set/get_instance_fallback reject it, step_counter needs dims <= 8.
+                                 eps is validated but unused: the model has no boundary and no clamp. */
 
 /* metrics: MetricType values (sympa/manifolds/metrics.py:6-12) */
 #define SYMPA_METRIC_RIEM 0

@@ -167,6 +167,7 @@ int launch_allpairs(const double* table, int64_t num_rows, const AllPairsArgs& a
 
 template <int N>
 int launch_allpairs_n(const double* table, int64_t num_rows, const AllPairsArgs& a, double* pack, int model, hipStream_t s) {
+    if (model == SYMPA_MODEL_DUAL) return launch_allpairs<N, sympa::MODEL_DUAL>(table, num_rows, a, pack, s);
     return model == SYMPA_MODEL_UPPER ? launch_allpairs<N, sympa::MODEL_UPPER>(table, num_rows, a, pack, s)
                                       : launch_allpairs<N, sympa::MODEL_BOUNDED>(table, num_rows, a, pack, s);
 }
@@ -182,7 +183,7 @@ extern "C" {
 
 int64_t sympa_all_pairs_workspace_bytes(int64_t num_rows, int n, int model) {
     if (num_rows <= 0 || n < 1 || n > SYMPA_MAX_DIMS_ALL_PAIRS_PACKED) return 0;
-    if (model != SYMPA_MODEL_UPPER && model != SYMPA_MODEL_BOUNDED) return 0;
+    if (model != SYMPA_MODEL_UPPER && model != SYMPA_MODEL_BOUNDED && model != SYMPA_MODEL_DUAL) return 0;
     return ((num_rows + 63) / 64) * 64 * (int64_t)pack_len(n, model) * 8;
 }
 
@@ -194,7 +195,7 @@ int sympa_all_pairs_dist_packed(const double* table, int64_t num_rows, int n, in
         return fail(SYMPA_ERR_BAD_ARG, "row block outside the table");
     if (row_count == 0) return 0;
     if (table == nullptr || out == nullptr) return fail(SYMPA_ERR_BAD_ARG, "null buffer");
-    if (model != SYMPA_MODEL_UPPER && model != SYMPA_MODEL_BOUNDED) return fail(SYMPA_ERR_BAD_ARG, "unknown model");
+    if (model != SYMPA_MODEL_UPPER && model != SYMPA_MODEL_BOUNDED && model != SYMPA_MODEL_DUAL) return fail(SYMPA_ERR_BAD_ARG, "unknown model");
     if (metric < SYMPA_METRIC_RIEM || metric > SYMPA_METRIC_WSUM) return fail(SYMPA_ERR_BAD_ARG, "unknown metric");
     if (metric == SYMPA_METRIC_WSUM && metric_w == nullptr) return fail(SYMPA_ERR_BAD_ARG, "metric wsum needs metric_w");
     if (!(eps > 0.0) || !(1.0 / eps < 1e300)) return fail(SYMPA_ERR_BAD_ARG, "eps must be > 0");

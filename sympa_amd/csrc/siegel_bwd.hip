@@ -4,6 +4,7 @@
 
 namespace sympa_hip {
 int launch_bwd_one_lane(const BwdArgs& a, int n, int model, bool scatter, hipStream_t s) {
+    if (model == SYMPA_MODEL_DUAL) return launch_bwd_dual(a, n, scatter, s);
     switch (n) {
         case 1: return launch_bwd_n<1>(a, model, scatter, s);
         case 2: return launch_bwd_n<2>(a, model, scatter, s);
@@ -37,7 +38,16 @@ int launch_bwd(const BwdArgs& a, int n, int model, bool scatter, void* workspace
         return fail(SYMPA_ERR_BAD_ARG, "SYMPA_FLAG_MERGE_SRC with grad_rows: only the one-pair-per-lane kernels of dims <= 6 write merged "
                                        "rows (no workspace / SYMPA_FLAG_SPLIT / SYMPA_FLAG_COOP / SYMPA_FLAG_GENERIC, dims <= 6)");
     };
-    if (merged_rows && (n > 6 || (a.f.flags & (SYMPA_FLAG_COOP | SYMPA_FLAG_SPLIT)))) return no_merge();
+    const bool dual = model == SYMPA_MODEL_DUAL;      // one pair per lane only: SYMPA_FLAG_COOP / SYMPA_FLAG_SPLIT / a workspace are ignored
+    if (merged_rows && (n > 6 || (!dual && (a.f.flags & (SYMPA_FLAG_COOP | SYMPA_FLAG_SPLIT))))) return no_merge();
+    if (dual) {
+        if (n > 8 && a.wave_partials != nullptr) return fail(SYMPA_ERR_UNSUPPORTED_DIMS, "wave_partials: dims 1..8");
+        if (n > 8 && a.f.batch_counter != nullptr)
+            return fail(SYMPA_ERR_UNSUPPORTED_DIMS, "step_counter at dims 9..16: the sixteen-lanes kernels only (none for the dual model)");
+        if (n >= 1 && n <= 8) return launch_bwd_one_lane(a, n, model, scatter, s);
+        if (n > 8 && n <= SYMPA_MAX_DIMS_BACKWARD) return launch_bwd_rolled(a, n, model, scatter, s);
+        return fail(SYMPA_ERR_UNSUPPORTED_DIMS, "backward: dims outside [1, SYMPA_MAX_DIMS_BACKWARD]");
+    }
     // Eight lanes per pair (two pairs per DPP row, no scratch) where measured faster than one pair per lane
     // (tools/bwd_coop_ab_small.py, per 262 144 pairs): the fused step at n = 8 (upper 1.78 -> 1.49 ms, bounded 2.59 -> 1.99 ms),
     // bounded n = 8 dense rows (2.51 -> 2.15 ms), bounded n = 7 fused (1.70 -> 1.56 ms).  SYMPA_FLAG_COOP forces it for

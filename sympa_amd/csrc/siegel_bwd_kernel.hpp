@@ -525,6 +525,8 @@ SYMPA_BWD_LARGE(7, upper)
 SYMPA_BWD_LARGE(7, bounded)
 SYMPA_BWD_LARGE(8, upper)
 SYMPA_BWD_LARGE(8, bounded)
+SYMPA_BWD_LARGE(7, dual)
+SYMPA_BWD_LARGE(8, dual)
 #undef SYMPA_BWD_LARGE
 
 // dims 5..8 with eight lanes per pair (siegel_bwd_half*.hip; A/B and, where faster, the default)
@@ -532,5 +534,10 @@ int launch_bwd_half(const BwdArgs& a, int n, int model, bool scatter, hipStream_
 
 // dims 9..16: siegel_bwd_rolled.hip (the same adjoint with rolled loops over scratch arrays)
 int launch_bwd_rolled(const BwdArgs& a, int n, int model, bool scatter, hipStream_t s);
+
+// compact dual: units of their own (siegel_bwd_dual.hip dims 1..6, siegel_bwd_n{7,8}_dual_{scatter,dense}.hip,
+// siegel_bwd_rolled_dual.hip dims 9..16), one pair per lane only
+int launch_bwd_dual(const BwdArgs& a, int n, bool scatter, hipStream_t s);
+int launch_bwd_rolled_dual(const BwdArgs& a, int n, bool scatter, hipStream_t s);
 
 }  // namespace sympa_hip

@@ -15,6 +15,7 @@ int launch_bwd_rolled_n(const BwdArgs& a, int model, bool scatter, hipStream_t s
 }
 
 int launch_bwd_rolled(const BwdArgs& a, int n, int model, bool scatter, hipStream_t s) {
+    if (model == SYMPA_MODEL_DUAL) return launch_bwd_rolled_dual(a, n, scatter, s);
     switch (n) {
         case 9: return launch_bwd_rolled_n<9>(a, model, scatter, s);
         case 10: return launch_bwd_rolled_n<10>(a, model, scatter, s);

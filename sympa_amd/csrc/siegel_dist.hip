@@ -22,7 +22,7 @@ int fail(int code, const char* msg) {
 int validate(const DistArgs& a, int model, int n) {
     if (a.b < 0) return fail(SYMPA_ERR_BAD_ARG, "negative batch size");
     if (a.base1 == nullptr || a.base2 == nullptr) return fail(SYMPA_ERR_BAD_ARG, "null buffer");
-    if (model != SYMPA_MODEL_UPPER && model != SYMPA_MODEL_BOUNDED) return fail(SYMPA_ERR_BAD_ARG, "unknown model");
+    if (model != SYMPA_MODEL_UPPER && model != SYMPA_MODEL_BOUNDED && model != SYMPA_MODEL_DUAL) return fail(SYMPA_ERR_BAD_ARG, "unknown model");
     if (a.metric < SYMPA_METRIC_RIEM || a.metric > SYMPA_METRIC_WSUM) return fail(SYMPA_ERR_BAD_ARG, "unknown metric");
     if (a.metric == SYMPA_METRIC_WSUM && a.metric_w == nullptr)
         return fail(SYMPA_ERR_BAD_ARG, "metric wsum needs metric_w");
@@ -87,7 +87,7 @@ int launch(const DistArgs& a, int n, int model, void* stream) {
     if (a.b < 0) return fail(SYMPA_ERR_BAD_ARG, "negative batch size");
     if (a.b == 0) return 0;
     if (a.base1 == nullptr || a.base2 == nullptr || a.out == nullptr) return fail(SYMPA_ERR_BAD_ARG, "null buffer");
-    if (model != SYMPA_MODEL_UPPER && model != SYMPA_MODEL_BOUNDED) return fail(SYMPA_ERR_BAD_ARG, "unknown model");
+    if (model != SYMPA_MODEL_UPPER && model != SYMPA_MODEL_BOUNDED && model != SYMPA_MODEL_DUAL) return fail(SYMPA_ERR_BAD_ARG, "unknown model");
     if (a.metric < SYMPA_METRIC_RIEM || a.metric > SYMPA_METRIC_WSUM) return fail(SYMPA_ERR_BAD_ARG, "unknown metric");
     if (a.metric == SYMPA_METRIC_WSUM && a.metric_w == nullptr)
         return fail(SYMPA_ERR_BAD_ARG, "metric wsum needs metric_w");
@@ -97,6 +97,17 @@ int launch(const DistArgs& a, int n, int model, void* stream) {
     if (n <= 4 && a.num_rows * 16 * n * n >= ((int64_t)1 << 32))
         return fail(SYMPA_ERR_BAD_ARG, "tables of dims <= 4 are limited to 4 GiB (32-bit row offsets in the gather)");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (model == SYMPA_MODEL_DUAL) {
+        // compact dual: one pair per lane (dims 1..8) and the runtime-n kernel (dims 9..16) only; SYMPA_FLAG_COOP is ignored
+        if (n >= 1 && n <= SYMPA_MAX_DIMS) return launch_dist_dual(a, n, s);
+        if (n > SYMPA_MAX_DIMS && n <= sympa::GENERIC_MAX_N) {
+            hipLaunchKernelGGL(siegel_dist_generic_kernel, dim3((unsigned)((a.b + 63) / 64)), dim3(64), 0, s, a, n, model);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return fail((int)e, hipGetErrorString(e));
+            return 0;
+        }
+        return fail(SYMPA_ERR_UNSUPPORTED_DIMS, "dims outside [1, SYMPA_MAX_DIMS_GENERIC]");
+    }
     if ((a.flags & SYMPA_FLAG_COOP) && (n == 7 || n == 8)) return launch_siegel_coop_half(a, n, model, s);   // A/B only: eight lanes per pair
     if ((a.flags & SYMPA_FLAG_COOP) && n == 6) return launch_siegel_coop(a, n, model, s);                 // A/B only: sixteen
     if (n >= 7 && n <= 8 && model == SYMPA_MODEL_UPPER && a.ap_cols == 0 && a.vvd == nullptr && a.batch_counter == nullptr &&
@@ -150,7 +161,7 @@ int launch_multi(const double* table, int64_t num_rows, int n, const int64_t* co
                  const double* scale, double scale_coef, double* const* out, int32_t* status, int flags, void* stream) {
     if (table == nullptr) return fail(SYMPA_ERR_BAD_ARG, "null buffer");
     if (num_rows <= 0) return fail(SYMPA_ERR_BAD_ARG, "empty table");
-    if (model != SYMPA_MODEL_UPPER && model != SYMPA_MODEL_BOUNDED) return fail(SYMPA_ERR_BAD_ARG, "unknown model");
+    if (model != SYMPA_MODEL_UPPER && model != SYMPA_MODEL_BOUNDED && model != SYMPA_MODEL_DUAL) return fail(SYMPA_ERR_BAD_ARG, "unknown model");
     if (metric < SYMPA_METRIC_RIEM || metric > SYMPA_METRIC_WSUM) return fail(SYMPA_ERR_BAD_ARG, "unknown metric");
     if (metric == SYMPA_METRIC_WSUM && metric_w == nullptr) return fail(SYMPA_ERR_BAD_ARG, "metric wsum needs metric_w");
     if (!(eps > 0.0) || !(1.0 / eps < 1e300)) return fail(SYMPA_ERR_BAD_ARG, "eps must be > 0");
@@ -191,6 +202,10 @@ int launch_multi(const double* table, int64_t num_rows, int n, const int64_t* co
     for (int i = k; i < SYMPA_MAX_FUSED_BATCHES; ++i) m.blk_end[i] = (unsigned)blocks;   // the search never lands there
     m.num_batches = k;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (model == SYMPA_MODEL_DUAL) {
+        if (n >= 1 && n <= SYMPA_MAX_DIMS) return launch_multi_dual(m, (unsigned)blocks, n, s);
+        return fail(SYMPA_ERR_UNSUPPORTED_DIMS, "fused batches need dims <= SYMPA_MAX_DIMS");
+    }
     if (n >= 7 && n <= 8 && model == SYMPA_MODEL_UPPER && !(flags & (SYMPA_FLAG_ANY_ORDER | SYMPA_FLAG_GENERIC))) {
         PackedArgs p;                       // the list form of the persistent dense forward (see launch())
         std::memset(&p, 0, sizeof(p));

@@ -167,7 +167,9 @@ hipError_t launch_kernel(K kern, unsigned grid, int block, const DistArgs& a, hi
     return hipGetLastError();
 }
 
-template <int N>
+// DUAL: the compact-dual instantiations live in units of their own (siegel_dist_dual.hip, siegel_dist_big_dual.hip), so the
+// units of the first two models compile exactly the kernels they did before the third existed
+template <int N, bool DUAL = false>
 int launch_n(const DistArgs& a, int model, hipStream_t s) {
     constexpr int FB = fwd_block(N);
     const unsigned grid = (unsigned)((a.b + FB - 1) / FB);
@@ -179,7 +181,10 @@ int launch_n(const DistArgs& a, int model, hipStream_t s) {
     // low-LDS gather when asked for, or when the grid is deep enough for a second block per CU to matter
     const bool low = DmaTile<N>::ENABLED && ((a.flags & SYMPA_FLAG_LOW_LDS) || grid > 2 * 256 * (BLOCK / FB));
     hipError_t e;
-    if (model == SYMPA_MODEL_UPPER) {
+    if constexpr (DUAL) {
+        if (low) e = launch_kernel(siegel_dist_kernel<N, sympa::MODEL_DUAL, true>, grid, FB, st, s);
+        else e = launch_kernel(siegel_dist_kernel<N, sympa::MODEL_DUAL, false>, grid, FB, st, s);
+    } else if (model == SYMPA_MODEL_UPPER) {
         if (low) e = launch_kernel(siegel_dist_kernel<N, sympa::MODEL_UPPER, true>, grid, FB, st, s);
         else e = launch_kernel(siegel_dist_kernel<N, sympa::MODEL_UPPER, false>, grid, FB, st, s);
     } else {
@@ -190,9 +195,11 @@ int launch_n(const DistArgs& a, int model, hipStream_t s) {
     return 0;
 }
 
-template <int N>
+template <int N, bool DUAL = false>
 int launch_multi_n(const MultiArgs& m, unsigned grid, int model, hipStream_t s) {
-    if (model == SYMPA_MODEL_UPPER)
+    if constexpr (DUAL)
+        hipLaunchKernelGGL((siegel_dist_multi_kernel<N, sympa::MODEL_DUAL>), dim3(grid), dim3(fwd_block(N)), 0, s, m);
+    else if (model == SYMPA_MODEL_UPPER)
         hipLaunchKernelGGL((siegel_dist_multi_kernel<N, sympa::MODEL_UPPER>), dim3(grid), dim3(fwd_block(N)), 0, s, m);
     else
         hipLaunchKernelGGL((siegel_dist_multi_kernel<N, sympa::MODEL_BOUNDED>), dim3(grid), dim3(fwd_block(N)), 0, s, m);
@@ -205,5 +212,10 @@ int launch_multi_n(const MultiArgs& m, unsigned grid, int model, hipStream_t s) 
 // siegel_dist_big.hip: dims 5..8
 int launch_dist_big(const DistArgs& a, int n, int model, hipStream_t s);
 int launch_multi_big(const MultiArgs& m, unsigned grid, int n, int model, hipStream_t s);
+// compact dual, dims 1..8: siegel_dist_dual.hip (1..4), siegel_dist_big_dual.hip (5..8)
+int launch_dist_dual(const DistArgs& a, int n, hipStream_t s);
+int launch_multi_dual(const MultiArgs& m, unsigned grid, int n, hipStream_t s);
+int launch_dist_big_dual(const DistArgs& a, int n, hipStream_t s);
+int launch_multi_big_dual(const MultiArgs& m, unsigned grid, int n, hipStream_t s);
 
 }  // namespace sympa_hip

@@ -48,7 +48,10 @@
 
 namespace sympa {
 
-enum Model : int { MODEL_UPPER = 0, MODEL_BOUNDED = 1 };
+// MODEL_DUAL: the compact dual (compact_dual.py:8), the bounded domain with the signs turned round: A = I + Z Z^H, sin(v_i) = sigma_i(E).
+// "Complex Hermitian factor" holds for bounded AND dual (tests of the form MODEL != MODEL_UPPER); the minus sign, the clamp at eps
+// and a projx that moves points are bounded only.
+enum Model : int { MODEL_UPPER = 0, MODEL_BOUNDED = 1, MODEL_DUAL = 2 };
 enum Metric : int { METRIC_RIEM = 0, METRIC_FONE = 1, METRIC_FINF = 2, METRIC_FMIN = 3, METRIC_WSUM = 4 };
 
 // status bits accumulated per launch (device counter words, see include/sympa_hip.h)
@@ -125,6 +128,39 @@ SYMPA_HD double d_log1p(double u) {
     return d_fma(kd, 6.93147180559945286227e-01, l);
 }
 
+// atan2(s, c) for s, c >= 0, not both 0: the angle in [0, pi/2], relative accuracy ~2 ulp at both ends (s -> 0 and c -> 0).
+// One reciprocal, no branch: with (num, den) = (min, max) of (s, c), t = num / den in [0, 1];
+//   t <= tan(pi/8): x = t;   otherwise atan(t) = pi/4 + atan(x), x = (num - den) / (num + den) in [-tan(pi/8), 0];
+// atan(x) = x - x z P(z), z = x^2, P = the 11-term minimax polynomial of the fdlibm/msun s_atan.c kernel (valid for |x| < 7/16);
+// s > c: the angle is pi/2 - atan(c / s).  pi/4 and pi/2 are added as hi + lo pairs.
+SYMPA_HD double d_atan2_pos(double s, double c) {
+    const bool swap = s > c;
+    const double num = swap ? c : s;
+    const double den = swap ? s : c;
+    const bool big = num > 0.41421356237309503 * den;
+    const double xn = big ? num - den : num;
+    const double xd = big ? num + den : den;
+    const double x = xn * d_rcp(xd);
+    const double z = x * x;
+    const double w = z * z;
+    double s1 = 1.62858201153657823623e-02;
+    s1 = d_fma(s1, w, 4.97687799461593236017e-02);
+    s1 = d_fma(s1, w, 6.66107313738753120669e-02);
+    s1 = d_fma(s1, w, 9.09088713343650656196e-02);
+    s1 = d_fma(s1, w, 1.42857142725034663711e-01);
+    s1 = d_fma(s1, w, 3.33333333333329318027e-01);
+    s1 = s1 * z;
+    double s2 = -3.65315727442169155270e-02;
+    s2 = d_fma(s2, w, -5.83357013379057348645e-02);
+    s2 = d_fma(s2, w, -7.69187620504482999495e-02);
+    s2 = d_fma(s2, w, -1.11111104054623557880e-01);
+    s2 = d_fma(s2, w, -1.99999999998764832476e-01);
+    s2 = s2 * w;
+    double a = d_fma(-x, s1 + s2, x);                                    // atan(x)
+    a = big ? 7.85398163397448278999e-01 + (a + 3.06161699786838301793e-17) : a;
+    return swap ? 1.57079632679489655800e+00 + (6.12323399573676603587e-17 - a) : a;
+}
+
 // A complex n x n matrix in registers: separate real / imaginary planes.
 template <int N>
 struct CMat {
@@ -182,18 +218,23 @@ SYMPA_UNROLL
     return ok;
 }
 
-// Cholesky of the Hermitian matrix A = I - W W^H for complex-symmetric W (bounded model).
-// (A)_ij = delta_ij - sum_l w_il conj(w_jl);  A = C C^H.
-template <int N>
-SYMPA_HD bool chol_id_minus_wwh(const CMat<N>& w, Tri<N, true>& c) {
+// Cholesky of the Hermitian matrix A = I - W W^H (bounded model) or, PLUS, A = I + W W^H (compact dual; always positive
+// definite) for complex-symmetric W.   (A)_ij = delta_ij -+ sum_l w_il conj(w_jl);  A = C C^H.
+template <bool PLUS>
+SYMPA_HD double wwh_sign(double x) {
+    if constexpr (PLUS) return x;
+    else return -x;
+}
+template <int N, bool PLUS>
+SYMPA_HD bool chol_id_pm_wwh(const CMat<N>& w, Tri<N, true>& c) {
     bool ok = true;
 SYMPA_UNROLL
     for (int j = 0; j < N; ++j) {
         double s = 1.0;
 SYMPA_UNROLL
         for (int l = 0; l < N; ++l) {
-            s = d_fma(-w.re[j][l], w.re[j][l], s);
-            s = d_fma(-w.im[j][l], w.im[j][l], s);
+            s = d_fma(wwh_sign<PLUS>(w.re[j][l]), w.re[j][l], s);
+            s = d_fma(wwh_sign<PLUS>(w.im[j][l]), w.im[j][l], s);
         }
 SYMPA_UNROLL
         for (int k = 0; k < j; ++k) {
@@ -205,14 +246,14 @@ SYMPA_UNROLL
         c.rdiag[j] = r;
 SYMPA_UNROLL
         for (int i = j + 1; i < N; ++i) {
-            // a_ij = - sum_l w_il conj(w_jl)          (i != j)
+            // a_ij = -+ sum_l w_il conj(w_jl)         (i != j)
             double tr = 0.0, ti = 0.0;
 SYMPA_UNROLL
             for (int l = 0; l < N; ++l) {
-                tr = d_fma(-w.re[i][l], w.re[j][l], tr);
-                tr = d_fma(-w.im[i][l], w.im[j][l], tr);
-                ti = d_fma(-w.im[i][l], w.re[j][l], ti);
-                ti = d_fma(w.re[i][l], w.im[j][l], ti);
+                tr = d_fma(wwh_sign<PLUS>(w.re[i][l]), w.re[j][l], tr);
+                tr = d_fma(wwh_sign<PLUS>(w.im[i][l]), w.im[j][l], tr);
+                ti = d_fma(wwh_sign<PLUS>(w.im[i][l]), w.re[j][l], ti);
+                ti = d_fma(-wwh_sign<PLUS>(w.re[i][l]), w.im[j][l], ti);
             }
             // minus sum_k c_ik conj(c_jk)
 SYMPA_UNROLL
@@ -227,6 +268,17 @@ SYMPA_UNROLL
         }
     }
     return ok;
+}
+
+template <int N>
+SYMPA_HD bool chol_id_minus_wwh(const CMat<N>& w, Tri<N, true>& c) { return chol_id_pm_wwh<N, false>(w, c); }
+template <int N>
+SYMPA_HD bool chol_id_plus_wwh(const CMat<N>& w, Tri<N, true>& c) { return chol_id_pm_wwh<N, true>(w, c); }
+// the complex Hermitian factor of a model that has one (bounded, dual)
+template <int N, int MODEL>
+SYMPA_HD bool chol_model_factor(const CMat<N>& w, Tri<N, true>& c) {
+    static_assert(MODEL == MODEL_BOUNDED || MODEL == MODEL_DUAL, "the upper model factors Im z (chol_real)");
+    return chol_id_pm_wwh<N, MODEL == MODEL_DUAL>(w, c);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -771,6 +823,15 @@ SYMPA_HD double vvd_from_sinh2(double lambda, double inv_eps) {
     return d_log1p(u);
 }
 
+// Compact dual: v = arcsin(sqrt(lambda)) = atan2(sqrt(lambda), sqrt(1 - lambda)) from lambda = sin^2(v), v in [0, pi/2]
+// (arctan of the reference's Takagi values d = tan v, compact_dual.py:60).  lambda is clamped into [0, 1] by the caller's
+// fmax and the fmin here (rounding can give 1 + 1e-16); the reference has no clamp and no eps in this model.
+// dv/dlambda = 1 / (2 sqrt(lambda (1 - lambda))) is unbounded at both ends: lambda -> 1 is the cut locus.
+SYMPA_HD double vvd_from_sin2(double lambda) {
+    const double lam = fmin(lambda, 1.0);
+    return d_atan2_pos(d_sqrt(lam), d_sqrt(1.0 - lam));
+}
+
 template <int N>
 SYMPA_HD void sort_ascending(double (&v)[N]) {
     // odd-even transposition network: N rounds, static indices
@@ -822,7 +883,7 @@ SYMPA_UNROLL
 // One pair, start to finish.  p1/p2 point at [2,n,n] fp64 points.  Returns the metric value; the
 // ascending vector-valued distance is written to vvd (if non-null) and status bits are OR-ed.
 // ---------------------------------------------------------------------------------------------
-// Second half of a pair: from E (sinh(v_i / 2) = sigma_i(E) / 2 upper, sigma_i(E) bounded) to the metric value.
+// Second half of a pair: from E (sinh(v_i / 2) = sigma_i(E) / 2 upper, sigma_i(E) bounded; sin(v_i) = sigma_i(E) dual) to the metric value.
 // From the Hermitian Gram matrix H = E^H E to the metric value (the packed forward evaluates this half in a kernel of its own,
 // csrc/siegel_packed_kernel.hpp: H is 2 n^2 registers where E and the factors are 6 n^2, so it runs two waves per SIMD).
 template <int N, int MODEL>
@@ -839,7 +900,8 @@ SYMPA_HD double distance_from_h(Herm<N>& h, const bool ok, int metric, const dou
 SYMPA_UNROLL
     for (int i = 0; i < N; ++i) {
         finite = finite && d_finite(h.d[i]);
-        v[i] = vvd_from_sinh2(fmax(h.d[i], 0.0) * scale, inv_eps);
+        if constexpr (MODEL == MODEL_DUAL) v[i] = vvd_from_sin2(fmax(h.d[i], 0.0));
+        else v[i] = vvd_from_sinh2(fmax(h.d[i], 0.0) * scale, inv_eps);
     }
     if (!finite) {
 SYMPA_UNROLL
@@ -873,7 +935,7 @@ SYMPA_HD double pair_distance_mats(const CMat<N>& z1, const CMat<N>& z2, int met
     CMat<N> e;
     bool ok;
     {
-        if (MODEL == MODEL_UPPER) {
+        if constexpr (MODEL == MODEL_UPPER) {
             Tri<N, false> l1, l2;
             ok = chol_real<N>(z1.im, l1);
             ok = chol_real<N>(z2.im, l2) && ok;
@@ -888,8 +950,8 @@ SYMPA_UNROLL
             solve_right_t<N, false>(l2, e);
         } else {
             Tri<N, true> c1, c2;
-            ok = chol_id_minus_wwh<N>(z1, c1);
-            ok = chol_id_minus_wwh<N>(z2, c2) && ok;
+            ok = chol_model_factor<N, MODEL>(z1, c1);
+            ok = chol_model_factor<N, MODEL>(z2, c2) && ok;
 SYMPA_UNROLL
             for (int i = 0; i < N; ++i)
 SYMPA_UNROLL
@@ -939,7 +1001,7 @@ SYMPA_UNROLL
     Tri<N, MODEL != MODEL_UPPER> l;
     bool ok;
     if constexpr (MODEL == MODEL_UPPER) ok = chol_real<N>(z.im, l);
-    else ok = chol_id_minus_wwh<N>(z, l);
+    else ok = chol_model_factor<N, MODEL>(z, l);
     // A = L^-1, column by column:  A[j][j] = 1 / L[j][j],   A[i][j] = -(1 / L[i][i]) sum_{k=j}^{i-1} L[i][k] A[k][j]
     double ar[N][N], ai[N][N];
 SYMPA_UNROLL

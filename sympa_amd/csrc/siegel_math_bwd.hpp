@@ -507,6 +507,19 @@ SYMPA_UNROLL
     for (int i = 0; i < N; ++i) {
         finite = finite && d_finite(lam_in[i]);     // before the clamp: fmax drops a NaN
         lam[i] = fmax(lam_in[i], 0.0);
+        if constexpr (MODEL == MODEL_DUAL) {
+            // v = arcsin(sqrt(lambda)), dv/dlambda = 1 / (2 sqrt(lambda (1 - lambda))).  lambda = 0 follows the convention of the
+            // other models (weight 0).  lambda >= 1 is the cut locus, where v is not differentiable: the weight is non-finite,
+            // so the pair's value and gradients come out NaN and ST_NONFINITE is raised -- never a silent zero.
+            const double l1m = fmin(lam[i], 1.0);
+            const double root = d_sqrt(l1m * (1.0 - l1m));
+            vv[i] = vvd_from_sin2(l1m);
+            const bool cut = !(lam[i] < 1.0);
+            dv[i] = (l1m > 0.0) ? 0.5 * d_rcp(root + TINY) : 0.0;
+            dv[i] = cut ? __builtin_nan("") : dv[i];
+            finite = finite && !cut;
+            continue;
+        }
         const double lp = lam[i] * scale;
         const double root = d_sqrt(d_fma(lp, lp, lp));       // sqrt(lp (1 + lp))
         double u = 2.0 * (lp + root);
@@ -701,7 +714,7 @@ template <int N, int MODEL, class Park = KeepFactors, class Unpark = KeepFactors
 SYMPA_HD double pair_backward(const CMat<N>& z1, const CMat<N>& z2, int metric, const double* __restrict__ w,
                               double inv_eps, double go, CMat<N>& g1, CMat<N>& g2, double (&gw)[N], int& status,
                               Park&& park = Park(), Unpark&& unpark = Unpark()) {
-    constexpr bool CPLX = (MODEL == MODEL_BOUNDED);
+    constexpr bool CPLX = (MODEL != MODEL_UPPER);     // complex Hermitian factor: bounded and dual
     Tri<N, CPLX> l1, l2;
     CMat<N> e;
     bool ok;
@@ -709,8 +722,8 @@ SYMPA_HD double pair_backward(const CMat<N>& z1, const CMat<N>& z2, int metric, 
         ok = chol_real<N>(z1.im, l1);
         ok = chol_real<N>(z2.im, l2) && ok;
     } else {
-        ok = chol_id_minus_wwh<N>(z1, l1);
-        ok = chol_id_minus_wwh<N>(z2, l2) && ok;
+        ok = chol_model_factor<N, MODEL>(z1, l1);
+        ok = chol_model_factor<N, MODEL>(z2, l2) && ok;
     }
 SYMPA_UNROLL
     for (int i = 0; i < N; ++i)
@@ -809,9 +822,11 @@ SYMPA_UNROLL
             }
     } else {
         // Wbar_1 = -Dbar - 2 A1bar W1,  Wbar_2 = Dbar - 2 A2bar W2, then symmetrise each plane
+        // (dual: A = I + W W^H, so dA = +(dW W^H + W dW^H) and the A-adjoint enters with the other sign: -+ Dbar + 2 Akbar Wk)
+        constexpr double ASIGN = (MODEL == MODEL_DUAL) ? 2.0 : -2.0;
         CMat<N> t1, t2;
-        cmatmul<N>(a1, z1, -2.0, t1);
-        cmatmul<N>(a2, z2, -2.0, t2);
+        cmatmul<N>(a1, z1, ASIGN, t1);
+        cmatmul<N>(a2, z2, ASIGN, t2);
 SYMPA_UNROLL
         for (int i = 0; i < N; ++i)
 SYMPA_UNROLL

@@ -55,6 +55,16 @@ SYMPA_HD void generic_factor_input(GenericWork& w, int n, int model, const doubl
             if (model == MODEL_UPPER) {              // Y = Im z
                 w.hr[gix(n, i, j)] = sym_at(im, n, i, j);
                 w.hi[gix(n, i, j)] = 0.0;
+            } else if (model == MODEL_DUAL) {         // A = I + W W^H,  a_ij = delta_ij + sum_l w_il conj(w_jl)
+                double tr = (i == j) ? 1.0 : 0.0, ti = 0.0;
+                for (int l = 0; l < n; ++l) {
+                    const double ar = sym_at(re, n, i, l), ai = sym_at(im, n, i, l);
+                    const double br = sym_at(re, n, j, l), bi = sym_at(im, n, j, l);
+                    tr += ar * br + ai * bi;
+                    ti += ai * br - ar * bi;
+                }
+                w.hr[gix(n, i, j)] = tr;
+                w.hi[gix(n, i, j)] = (i == j) ? 0.0 : ti;
             } else {                                  // A = I - W W^H,  a_ij = delta_ij - sum_l w_il conj(w_jl)
                 double tr = (i == j) ? 1.0 : 0.0, ti = 0.0;
                 for (int l = 0; l < n; ++l) {
@@ -163,7 +173,8 @@ SYMPA_HD double pair_distance_generic(GenericWork& w, const double* __restrict__
     bool finite = true;          // tested before the clamp: fmax would turn a NaN eigenvalue into distance 0
     for (int i = 0; i < n; ++i) {
         finite = finite && d_finite(w.hr[gix(n, i, i)]);
-        w.v[i] = vvd_from_sinh2(fmax(w.hr[gix(n, i, i)], 0.0) * scale, inv_eps);
+        const double lam = fmax(w.hr[gix(n, i, i)], 0.0);
+        w.v[i] = (model == MODEL_DUAL) ? vvd_from_sin2(lam) : vvd_from_sinh2(lam * scale, inv_eps);
     }
     for (int i = 1; i < n; ++i) {            // insertion sort, ascending
         const double x = w.v[i];

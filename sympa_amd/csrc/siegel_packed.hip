@@ -35,6 +35,7 @@ int pack_n(const double* table, int64_t num_rows, int model, double* pack, int32
 int pack_any(const double* table, int64_t num_rows, int n, int model, void* pack, int64_t pack_bytes, int32_t* status,
              const unsigned* guard, hipStream_t s) {
     if (!packed_dims_ok(n)) return fail(SYMPA_ERR_UNSUPPORTED_DIMS, "packed table: dims 5..8");
+    if (model == SYMPA_MODEL_DUAL) return fail(SYMPA_ERR_BAD_ARG, "the compact dual model has no packed path: use sympa_model_forward");
     if (model != SYMPA_MODEL_UPPER && model != SYMPA_MODEL_BOUNDED) return fail(SYMPA_ERR_BAD_ARG, "unknown model");
     if (table == nullptr || num_rows <= 0) return fail(SYMPA_ERR_BAD_ARG, "empty table");
     if (pack == nullptr || pack_bytes < sympa_table_pack_bytes(num_rows, n, model) || (reinterpret_cast<uintptr_t>(pack) & 15))
@@ -59,6 +60,7 @@ int forward_n(const PackedArgs& a, unsigned grid, int model, hipStream_t s) {
 int check_common(const void* pack, int64_t pack_bytes, int64_t num_rows, int n, int model, int metric, const double* metric_w,
                  double eps, const double* scale, double scale_coef) {
     if (!packed_dims_ok(n)) return fail(SYMPA_ERR_UNSUPPORTED_DIMS, "packed forward: dims 5..8");
+    if (model == SYMPA_MODEL_DUAL) return fail(SYMPA_ERR_BAD_ARG, "the compact dual model has no packed path: use sympa_model_forward");
     if (model != SYMPA_MODEL_UPPER && model != SYMPA_MODEL_BOUNDED) return fail(SYMPA_ERR_BAD_ARG, "unknown model");
     if (num_rows <= 0) return fail(SYMPA_ERR_BAD_ARG, "empty table");
     if (num_rows > (int64_t)0x7fffffff) return fail(SYMPA_ERR_BAD_ARG, "more than 2^31-1 table rows");

@@ -175,9 +175,18 @@ int dispatch_table(int op, int n, int model, double* z, const double* g, double*
     if (b < 0) return fail(SYMPA_ERR_BAD_ARG, "negative row count");
     if (b == 0) return 0;
     if (z == nullptr) return fail(SYMPA_ERR_BAD_ARG, "null buffer");
-    if (model != SYMPA_MODEL_UPPER && model != SYMPA_MODEL_BOUNDED) return fail(SYMPA_ERR_BAD_ARG, "unknown model");
+    if (model != SYMPA_MODEL_UPPER && model != SYMPA_MODEL_BOUNDED && model != SYMPA_MODEL_DUAL) return fail(SYMPA_ERR_BAD_ARG, "unknown model");
     if (b > (int64_t)0x7fffffff * BLOCK) return fail(SYMPA_ERR_BAD_ARG, "too many rows for one launch");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (model == SYMPA_MODEL_DUAL) {
+        // compact dual: one row per lane at every dims (no lanes-per-row instances); projx only symmetrises and never counts a row
+        if (op == 3) return fail(SYMPA_ERR_BAD_ARG, "the compact dual model has no inner product (the reference's inner raises "
+                                                    "NotImplementedError, compact_dual.py:96): no tangent norm, no RiemannianAdam");
+        if (n >= 1 && n <= 8) return launch_table_dual(op, n, z, g, out, b, lr, wd, eps, projected, status, s, clip, max_norm);
+        if (n > 8 && n <= SYMPA_MAX_DIMS_GENERIC)
+            return launch_table_rolled_dual(op, n, z, g, out, b, lr, wd, eps, projected, status, s, clip, max_norm);
+        return fail(SYMPA_ERR_UNSUPPORTED_DIMS, "dims outside [1, SYMPA_MAX_DIMS_GENERIC]");
+    }
     static const bool generic = std::getenv("SYMPA_TABLE_GENERIC") != nullptr;      // one-row-per-lane kernels for A/B
     // projx / the RSGD step at dims >= 7 need the caller's scratch word `outside`; without it they run the one-row-per-lane
     // kernels below (exact, every row through the eigenvalue clamp, slower)
@@ -261,6 +270,7 @@ int sympa_radam_step(double* table, const double* grad, double* exp_avg, double*
     if (num_rows == 0) return 0;
     if (table == nullptr || grad == nullptr || exp_avg == nullptr || exp_avg_sq == nullptr || bias_pows == nullptr)
         return fail(SYMPA_ERR_BAD_ARG, "null buffer");
+    if (model == SYMPA_MODEL_DUAL) return fail(SYMPA_ERR_BAD_ARG, "the compact dual model has no inner product (the reference's inner raises NotImplementedError, compact_dual.py:96): RiemannianAdam and the fused step do not exist for it");
     if (model != SYMPA_MODEL_UPPER && model != SYMPA_MODEL_BOUNDED) return fail(SYMPA_ERR_BAD_ARG, "unknown model");
     if (!(eps > 0.0) || !(eps_adam >= 0.0)) return fail(SYMPA_ERR_BAD_ARG, "eps must be > 0, the Adam epsilon >= 0");
     if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return fail(SYMPA_ERR_BAD_ARG, "betas must lie in [0, 1)");
@@ -382,6 +392,7 @@ int fused_step_impl(double* table, double* grad, int64_t num_rows, int n, int mo
             return fail(SYMPA_ERR_BAD_ARG, "null Adam state of the plain parameters");
     }
     if (sq_partials != nullptr && num_sq_partials < 1) return fail(SYMPA_ERR_BAD_ARG, "empty partial list");
+    if (model == SYMPA_MODEL_DUAL) return fail(SYMPA_ERR_BAD_ARG, "the compact dual model has no inner product (the reference's inner raises NotImplementedError, compact_dual.py:96): RiemannianAdam and the fused step do not exist for it");
     if (model != SYMPA_MODEL_UPPER && model != SYMPA_MODEL_BOUNDED) return fail(SYMPA_ERR_BAD_ARG, "unknown model");
     if (!(eps > 0.0)) return fail(SYMPA_ERR_BAD_ARG, "eps must be > 0");
     if (num_extra < 0 || num_extra > FUSED_MAX_EXTRA) return fail(SYMPA_ERR_BAD_ARG, "at most 2 plain parameters");

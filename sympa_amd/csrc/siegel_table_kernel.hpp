@@ -393,13 +393,20 @@ int launch_fused_step(const FusedStepArgs& a, int model, int block, hipStream_t 
     return 0;
 }
 
-template <int N>
+// DUAL: the compact-dual instantiations (siegel_table_dual.hip, siegel_table_rolled_dual.hip); op 3 (the tangent norm) does not
+// exist for that model
+template <int N, bool DUAL = false>
 int launch_table(int op, int model, double* z, const double* g, double* out, int64_t b, double lr, double wd,
                  double eps, int32_t* projected, int32_t* status, hipStream_t s, const double* clip, double max_norm,
                  const int* gate = nullptr) {
     const unsigned grid = (unsigned)((b + BLOCK - 1) / BLOCK);
     const bool up = model == SYMPA_MODEL_UPPER;
-    if (op == 3) {
+    if constexpr (DUAL) {
+        if (op == 2) hipLaunchKernelGGL((egrad2rgrad_kernel<N, sympa::MODEL_DUAL>), dim3(grid), dim3(BLOCK), 0, s, z, g, out, b);
+        else if (op == 0) hipLaunchKernelGGL((table_update_kernel<N, sympa::MODEL_DUAL, 0>), dim3(grid), dim3(BLOCK), 0, s, z, g, out, b, lr, wd, eps, projected, status, clip, max_norm, gate);
+        else if (op == 1) hipLaunchKernelGGL((table_update_kernel<N, sympa::MODEL_DUAL, 1>), dim3(grid), dim3(BLOCK), 0, s, z, g, out, b, lr, wd, eps, projected, status, clip, max_norm, gate);
+        else return fail(SYMPA_ERR_BAD_ARG, "the compact dual model has no inner product (the reference's inner raises NotImplementedError)");
+    } else if (op == 3) {
         if (up) hipLaunchKernelGGL((tangent_sqnorm_kernel<N, sympa::MODEL_UPPER>), dim3(grid), dim3(BLOCK), 0, s, z, g, out, b, status);
         else hipLaunchKernelGGL((tangent_sqnorm_kernel<N, sympa::MODEL_BOUNDED>), dim3(grid), dim3(BLOCK), 0, s, z, g, out, b, status);
     } else if (op == 2) {
@@ -421,6 +428,11 @@ int launch_table(int op, int model, double* z, const double* g, double* out, int
 int launch_table_rolled(int op, int n, int model, double* z, const double* g, double* out, int64_t b, double lr, double wd,
                         double eps, int32_t* projected, int32_t* status, hipStream_t s, const double* clip, double max_norm,
                         const int* gate = nullptr);
+// compact dual, one row per lane: n = 1..8 (siegel_table_dual.hip), n = 9..16 (siegel_table_rolled_dual.hip)
+int launch_table_dual(int op, int n, double* z, const double* g, double* out, int64_t b, double lr, double wd, double eps,
+                      int32_t* projected, int32_t* status, hipStream_t s, const double* clip, double max_norm);
+int launch_table_rolled_dual(int op, int n, double* z, const double* g, double* out, int64_t b, double lr, double wd, double eps,
+                             int32_t* projected, int32_t* status, hipStream_t s, const double* clip, double max_norm);
 // n = 9..16, op 1 (RSGD step) and 2 (egrad2rgrad) with sixteen lanes per row (siegel_table_coop_{upper,bounded}.hip);
 // `outside`: device word that receives the number of rows that left the eps-interior (op 1)
 int launch_table_coop_upper(int op, int n, double* z, const double* g, double* out, int64_t b, double lr, double wd, double eps,

@@ -6,6 +6,9 @@
 //   bounded: egrad2rgrad = A G A,  A = I - conj(Z) Z               sympa/manifolds/bounded_domain.py:41-53,163-170
 //            projx = symmetrise, then clamp the Takagi values of Z at 1 - eps, untouched when all < 1 - eps
 //                    (intended behaviour of bounded_domain.py:55-84; the in-tree call is broken)
+//   dual   : egrad2rgrad = (I + conj(Z) Z) G (I + Z conj(Z))       sympa/manifolds/compact_dual.py:64-79
+//            projx = symmetrise only: every symmetric matrix is a point (siegel_manifold.py:130-137); never counts a row
+//            inner is not implemented by the reference (compact_dual.py:96): no tangent_sqnorm, no Adam
 //   retr   = projx(x + u)                                           sympa/manifolds/siegel_manifold.py:74-87
 //   RSGD step (geoopt.optim.RiemannianSGD with momentum 0, the optimiser train.py:66-68 builds):
 //            x <- retr(x, -lr * egrad2rgrad(x, grad + weight_decay * x))
@@ -119,10 +122,21 @@ SYMPA_UNROLL
         for (int i = 0; i < N; ++i)
 SYMPA_UNROLL
             for (int j = 0; j < N; ++j) { zc.re[i][j] = z.re[i][j]; zc.im[i][j] = -z.im[i][j]; }
-        cmatmul<N>(zc, z, -1.0, a);              // -conj(Z) Z
+        cmatmul<N>(zc, z, MODEL == MODEL_DUAL ? 1.0 : -1.0, a);              // -+ conj(Z) Z
 SYMPA_UNROLL
         for (int i = 0; i < N; ++i) a.re[i][i] += 1.0;
         cmatmul<N>(a, u, 1.0, t);
+        if constexpr (MODEL == MODEL_DUAL) {
+            // right factor I + Z conj(Z) = A^T (A Hermitian, Z symmetric): transpose a in place, then the same product
+SYMPA_UNROLL
+            for (int i = 0; i < N; ++i)
+SYMPA_UNROLL
+                for (int j = i + 1; j < N; ++j) {
+                    const double r = a.re[i][j], m = a.im[i][j];
+                    a.re[i][j] = a.re[j][i]; a.im[i][j] = a.im[j][i];
+                    a.re[j][i] = r;          a.im[j][i] = m;
+                }
+        }
         cmatmul<N>(t, a, 1.0, out);
     }
 }
@@ -132,6 +146,9 @@ SYMPA_UNROLL
 template <int N, int MODEL>
 SYMPA_HD bool projx(CMat<N>& z, double eps, int& status) {
     symmetrise<N>(z);
+    if constexpr (MODEL == MODEL_DUAL) {
+        return false;      // no boundary: nothing to clamp, nothing to count
+    } else {
     // Cheap certificate first: the row is inside the eps-interior iff a Cholesky factorisation exists (upper: Im z - eps I
     // positive definite <=> every eigenvalue > eps; bounded: I - Z Z^H / (1 - eps)^2 positive definite <=> every Takagi value
     // < 1 - eps).  When it holds for all 64 rows of the wave -- every step of a converging run -- the eigendecomposition
@@ -225,6 +242,7 @@ SYMPA_UNROLL
         symmetrise<N>(z);
         return true;
     }
+    }
 }
 
 // ---- one RSGD step on one row --------------------------------------------------------------------
@@ -259,6 +277,7 @@ SYMPA_UNROLL
 // (geoopt Manifold.component_inner = inner broadcast over the point).
 template <int N, int MODEL>
 SYMPA_HD double tangent_sqnorm(const CMat<N>& z, const CMat<N>& u, int& status) {
+    static_assert(MODEL != MODEL_DUAL, "the compact dual has no inner product in the reference (compact_dual.py:96)");
     CMat<N> e;
     bool ok;
     if (MODEL == MODEL_UPPER) {

@@ -9,7 +9,7 @@ import torch
 import torch.nn as nn
 
 from sympa_amd import config
-from sympa_amd.manifolds import BoundedDomainManifold, SymmetricPositiveDefinite, UpperHalfManifold
+from sympa_amd.manifolds import BoundedDomainManifold, CompactDualManifold, SymmetricPositiveDefinite, UpperHalfManifold
 from sympa_amd.manifolds.base import ManifoldParameter
 from sympa_amd.manifolds.metrics import MetricType
 
@@ -43,7 +43,7 @@ class Embeddings(nn.Module, abc.ABC):
         return (True, None, None) if ok else (False, point, reason)
 
     def _first_bad_row(self, pts, atol=1e-5, rtol=1e-5):
-        from sympa_amd.manifolds import SymmetricPositiveDefinite, UpperHalfManifold
+        from sympa_amd.manifolds import CompactDualManifold, SymmetricPositiveDefinite, UpperHalfManifold
         diff = (pts - pts.transpose(-1, -2)).abs()
         tol = atol + rtol * pts.transpose(-1, -2).abs()
         flat = (diff > tol).reshape(len(pts), -1).any(dim=1)              # torch.allclose, row by row
@@ -51,6 +51,8 @@ class Embeddings(nn.Module, abc.ABC):
             flat |= ~(torch.linalg.det(pts[:, 1]) > 0)                     # upper_half.py:108-113
         elif isinstance(self.manifold, SymmetricPositiveDefinite):
             flat |= ~(torch.linalg.eigvalsh(pts) > -atol).all(dim=-1)
+        elif isinstance(self.manifold, CompactDualManifold):
+            pass                                                           # compact_dual.py:81-93: symmetry is the whole test
         else:                                                              # bounded_domain.py:141-149
             zc = torch.complex(pts[:, 0], pts[:, 1])
             a = torch.eye(pts.shape[-1], dtype=zc.dtype, device=pts.device) - zc.conj() @ zc
@@ -92,8 +94,9 @@ class EmbeddingsFactory:
 
 
 class ManifoldFactory:
-    sympa_manifolds = {"upper": UpperHalfManifold, "bounded": BoundedDomainManifold}   # embeddings.py:145-149
-    out_of_scope = {"dual", "euclidean", "poincare", "lorentz", "sphere",
+    sympa_manifolds = {"upper": UpperHalfManifold, "bounded": BoundedDomainManifold,
+                       "dual": CompactDualManifold}                                   # embeddings.py:145-149
+    out_of_scope = {"euclidean", "poincare", "lorentz", "sphere",
                     "prod-hysph", "prod-hyhy", "prod-hyeu", "prod-sphsph"}
 
     @classmethod

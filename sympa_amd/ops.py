@@ -15,7 +15,9 @@ from sympa_amd import _lib
 from sympa_amd import selfcheck as _sc
 from sympa_amd.config import EPS
 
-MODEL_IDS = {"upper": 0, "bounded": 1}
+MODEL_IDS = {"upper": 0, "bounded": 1, "dual": 2}
+# the compact dual runs the one-pair-per-lane and runtime-n kernels only: no packed table, no lanes-per-pair instances, no fused step
+LANES_PER_PAIR_MODELS = ("upper", "bounded")
 METRIC_IDS = {"riem": 0, "fone": 1, "finf": 2, "fmin": 3, "wsum": 4}
 
 ST_NOT_PD, ST_NONFINITE, ST_BAD_INDEX, ST_NO_CONVERGENCE = 1, 2, 4, 8
@@ -62,6 +64,8 @@ def check_status(device=None, reset=True):
 def _gate(family, model, n, dev):
     """First use of a lanes-per-pair kernel instantiation on a device: compare it with the one-lane kernel
     (sympa_amd/selfcheck.py).  One tuple lookup afterwards; dims below the family's range cost one comparison."""
+    if model not in LANES_PER_PAIR_MODELS and model != "spd":
+        return                           # dual: there is no lanes-per-pair instance to compare or to demote
     if n >= _sc.RANGE[family][0] and (family, model, n, dev.index) not in _sc.CHECKED:
         _sc.ensure(family, model, n, dev)
 
@@ -345,7 +349,7 @@ class PackedTable:
 
     @staticmethod
     def supported(table, model):
-        return (model in MODEL_IDS and table.is_cuda and table.dtype == torch.float64 and table.dim() == 4 and table.shape[1] == 2
+        return (model in LANES_PER_PAIR_MODELS and table.is_cuda and table.dtype == torch.float64 and table.dim() == 4 and table.shape[1] == 2
                 and table.shape[2] == table.shape[3] and 5 <= table.shape[2] <= 8 and table.is_contiguous())
 
     def __init__(self, model):

@@ -109,6 +109,13 @@ class RiemannianAdam(torch.optim.Optimizer):
             raise NotImplementedError("amsgrad is not built")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, step=0))
         self._stabilize = stabilize
+        for group in self.param_groups:
+            for p in group["params"]:
+                if getattr(getattr(p, "manifold", None), "model_name", None) == "dual":
+                    raise NotImplementedError(
+                        "RiemannianAdam needs the manifold's inner product for its second moment, and the compact dual model has "
+                        "none (the reference's CompactDualManifold.inner raises NotImplementedError, compact_dual.py:96); use "
+                        "RiemannianSGD")
 
     def _init_param_state(self, p, betas, steps_taken=0):
         """Creates whatever the state of `p` lacks (all of it on first use; `bias_pows` / `betas` when the state came from

@@ -114,7 +114,7 @@ class GraphedTrainStep:
         man = m.manifold
         table = m.embeddings.embeds
         if not isinstance(self.opt, (RiemannianSGD, RiemannianAdam)) or getattr(man, "model_name", None) not in ("upper", "bounded"):
-            return False
+            return False            # (dual declines here and runs the classic backward kernel + optimiser kernel: no fused step, no Adam)
         if isinstance(self.opt, RiemannianAdam) and len({(tuple(g["betas"]), g["eps"]) for g in self.opt.param_groups}) != 1:
             return False            # one set of Adam hyper-parameters per launch
         if not ops.FusedStep.supported(table.data):
@@ -231,12 +231,14 @@ class GraphedTrainStep:
         """Classic graph of a Siegel model on the GPU with dims <= 8 or the sixteen-lanes kernels (every family that honours the
         batch window; the rolled one-lane kernels of dims 9..16 behind an instance fallback do not)."""
         m = self.model
-        if self.mode != "classic" or getattr(m.manifold, "model_name", None) not in ("upper", "bounded") or self.deterministic:
+        if self.mode != "classic" or getattr(m.manifold, "model_name", None) not in ("upper", "bounded", "dual") or self.deterministic:
             return False
         table = m.embeddings.embeds
         if not (table.is_cuda and table.dim() == 4 and table.dtype == torch.float64):
             return False
         n = table.shape[2]
+        if m.manifold.model_name == "dual":
+            return n <= 8                # dims 9..16 run the rolled one-lane kernels only, which do not honour the batch window
         if n > 8 and _lib.load().sympa_get_instance_fallback(_sc.SIEGEL_BWD, ops.MODEL_IDS[m.manifold.model_name], int(n)):
             return False
         return True
@@ -525,7 +527,7 @@ class DistributedTrainStep:
         from sympa_amd.optim import RiemannianSGD
         man = model.manifold
         table = model.embeddings.embeds
-        if getattr(man, "model_name", None) not in ("upper", "bounded", "spd"):
+        if getattr(man, "model_name", None) not in ("upper", "bounded", "dual", "spd"):
             raise NotImplementedError("DistributedTrainStep: the Siegel models and spd")
         self.spd = man.model_name == "spd"
         if self.spd and mode == "auto":
@@ -583,7 +585,9 @@ class DistributedTrainStep:
             self.gd_b = torch.ones(self.batch_size, dtype=torch.float64, device=device)
             need = int(ops._lib.load().sympa_spd_backward_workspace_bytes(self.batch_size, table.shape[1]))
             self.spd_ws = torch.empty(need, dtype=torch.uint8, device=device) if need > 0 else None
-        if not self.spd and self.mode != "sharded" and ops.FusedStep.supported(table.data) and len(self._extra) <= 2 and \
+        # (the dual model has no fused optimiser kernel: its step stays the separate clip + RSGD kernels)
+        if not self.spd and man.model_name != "dual" and self.mode != "sharded" and ops.FusedStep.supported(table.data) and \
+                len(self._extra) <= 2 and \
                 all(p.numel() <= 64 for p in self._extra):
             self._fused = ops.FusedStep(table.data, table.grad, man.model_name, [(p.data, p.grad) for p in self._extra],
                                         counter=self.counter, projected=man.projected_counter(table.device), zero_grads=True)
