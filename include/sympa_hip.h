@@ -547,6 +547,31 @@ int sympa_map_rows(const double* dist, int64_t row_count, int64_t ld, int64_t ro
                    const int64_t* rowptr, const int32_t* cols, int64_t max_degree, double* ap, void* workspace,
                    int64_t workspace_bytes, int32_t* status, int flags, void* stream);
 
+/* Hop distances (unweighted shortest paths) from the sources src_begin .. src_begin + src_count - 1 to every node of a graph:
+ * what the reference's preprocessing computes for all pairs at once (preprocess.py:101-126), a block of rows at a time
+ * (csrc/graph_bfs.hip: level-synchronous bit-parallel BFS, one workgroup per word of 64 sources).
+ *   rowptr      [num_nodes + 1] int64, cols [num_entries] int32: the adjacency as a SYMMETRIC CSR (both directions of every
+ *               edge present), self-loops and duplicate edges removed
+ *   out         [src_count, row_stride] int32, row_stride >= num_nodes: out[s - src_begin][v] = hops from s to v, 0 on the
+ *               diagonal, -1 where v cannot be reached.  Every element [r][v < num_nodes] is written; nothing is pre-filled.
+ *   workspace   sympa_graph_hops_workspace_bytes(num_nodes, src_count) = ceil(src_count / 64) * 24 * num_nodes bytes of
+ *               caller-owned, 8-byte aligned device memory (three uint64 node planes per word of sources)
+ * The values do not depend on how the sources are split into calls.  A column outside [0, num_nodes) or a rowptr entry outside
+ * [0, num_entries] is skipped and sets SYMPA_ST_BAD_INDEX in `status` (word 1 counts the entries).  Arguments are validated
+ * before any launch. */
+int64_t sympa_graph_hops_workspace_bytes(int64_t num_nodes, int64_t src_count);
+int sympa_graph_hop_rows(const int64_t* rowptr, const int32_t* cols, int64_t num_nodes, int64_t num_entries, int64_t src_begin,
+                         int64_t src_count, int32_t* out, int64_t row_stride, void* workspace, int64_t workspace_bytes,
+                         int32_t* status, void* stream);
+
+/* Distortion of a block of manifold distance rows against the hop rows of the same nodes (metrics.py:21 over the pairs i < j):
+ *   row_sum[r]   = sum over j > i, hops[r][j] > 0 of |dist[r][j] - hops[r][j]| / hops[r][j],   i = row_begin + r
+ *   row_pairs[r] = the number of those j
+ * dist [row_count, ld_dist] fp64, hops [row_count, ld_hops] int32 (sympa_graph_hop_rows), both leading dimensions >= num_nodes.
+ * Each row is summed in an order that depends on the row alone, so a row's value is bitwise the same in every blocking. */
+int sympa_graph_distortion_rows(const double* dist, int64_t ld_dist, const int32_t* hops, int64_t ld_hops, int64_t row_begin,
+                                int64_t row_count, int64_t num_nodes, double* row_sum, int64_t* row_pairs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -122,6 +122,10 @@ def named_graph(name):
         return nx.balanced_tree(3, 6)
     if name == "margulis-71":
         return nx.margulis_gabber_galil_graph(71)
+    if name == "product-cartesian-45500":
+        # preprocess.py:53-60: 364 tree nodes x 125 grid nodes.  Too large for graph_triplets (a dense fp64 [N, N] matrix):
+        # its distances come from sympa_amd.graph.GraphDistances, a block of rows at a time
+        return nx.cartesian_product(nx.balanced_tree(3, 5), nx.grid_graph(dim=[5, 5, 5]))
     raise KeyError(name)
 
 

@@ -1,0 +1,223 @@
+"""Graph hop distances a block of source rows at a time: the preprocessing side of the path (preprocess.py:101-126) for graphs
+whose all-pairs matrix does not fit.
+
+`data.graph_triplets` computes every pair at once through scipy and a dense fp64 [N, N] matrix, which is fine up to a few
+thousand nodes.  Here the same distances come out of a bit-parallel multi-source BFS over a CSR (csrc/graph_bfs.hip through
+ops.graph_hop_rows), R source rows per call, so the 45 500-node product graph of configs[3] can label its own pairs, be ranked
+against itself and be scored over all of its pairs without the matrix ever existing.
+
+  graph_csr(graph)             networkx graph -> (rowptr, cols, id2node), relabelled and cleaned exactly like graph_triplets
+  host_hop_rows(...)           the numpy restatement of the kernel's algorithm (CPU tests, CPU tensors)
+  GraphDistances(rowptr, cols) rows / pairs / triplets / neighbor_csr on the CSR's device
+"""
+import numpy as np
+import torch
+
+# default cap on what GraphDistances.triplets() may return: 24 bytes per triplet
+TRIPLETS_MAX_BYTES = 2 << 30
+
+
+def graph_csr(graph):
+    """(rowptr int64 [N + 1], cols int32 [E], id2node) of a networkx graph as CPU tensors: nodes relabelled by sorted(), parallel
+    edges collapsed (nx.Graph), self-loops dropped, both directions of every edge stored, each row's columns ascending -- the
+    cleaning of data.graph_triplets.  Edge weights are not supported here."""
+    import networkx as nx
+
+    nodes = sorted(graph.nodes())
+    id2node = {i: node for i, node in enumerate(nodes)}
+    g = nx.Graph(nx.convert_node_labels_to_integers(graph, ordering="sorted"))
+    if any("weight" in d for _, _, d in g.edges(data=True)):
+        raise NotImplementedError("graph_csr computes hop distances of unweighted graphs only; "
+                                  "use data.graph_triplets for a weighted graph")
+    N = len(nodes)
+    e = np.array([(u, v) for u, v in g.edges() if u != v], dtype=np.int64).reshape(-1, 2)
+    key = np.unique(np.concatenate((e[:, 0] * N + e[:, 1], e[:, 1] * N + e[:, 0])))
+    rows = key // max(N, 1)
+    rowptr = np.zeros(N + 1, dtype=np.int64)
+    rowptr[1:] = np.cumsum(np.bincount(rows, minlength=N))
+    cols = (key - rows * N).astype(np.int32)
+    return torch.from_numpy(rowptr), torch.from_numpy(cols), id2node
+
+
+def host_hop_rows(rowptr, cols, begin, count):
+    """int32 [count, N] ndarray of hop distances from the sources [begin, begin + count): 0 on the diagonal, -1 for unreachable
+    nodes.  The algorithm of csrc/graph_bfs.hip in numpy: per word of 64 sources one uint64 per node for `seen` and the frontier,
+    every level ORs the neighbours' frontier words per node (pull), masks with ~seen and writes the level for every new bit.
+    Columns outside [0, N) are skipped, as the kernel skips them."""
+    rowptr = np.asarray(rowptr.cpu() if torch.is_tensor(rowptr) else rowptr).astype(np.int64)
+    cols = np.asarray(cols.cpu() if torch.is_tensor(cols) else cols).astype(np.int64)
+    N = rowptr.size - 1
+    begin, count = int(begin), int(count)
+    if N <= 0 or begin < 0 or count < 0 or begin + count > N:
+        raise ValueError(f"source block [{begin}, {begin + count}) outside [0, {N})")
+    out = np.full((count, N), -1, dtype=np.int32)
+    deg = rowptr[1:] - rowptr[:-1]
+    owner = np.repeat(np.arange(N), deg)
+    ok = (cols >= 0) & (cols < N)
+    owner, nbr = owner[ok], cols[ok]
+    starts = np.flatnonzero(np.r_[True, owner[1:] != owner[:-1]]) if owner.size else np.zeros(0, np.int64)
+    pulled = owner[starts] if owner.size else owner
+    shifts = np.arange(64, dtype=np.uint64)[:, None]
+    for w0 in range(0, count, 64):
+        nbits = min(64, count - w0)
+        seen = np.zeros(N, dtype=np.uint64)
+        src = np.arange(nbits)
+        seen[begin + w0 + src] = np.uint64(1) << src.astype(np.uint64)
+        out[w0 + src, begin + w0 + src] = 0
+        cur = seen.copy()
+        block = out[w0:w0 + nbits]
+        for level in range(1, N):
+            f = np.zeros(N, dtype=np.uint64)
+            if owner.size:
+                f[pulled] = np.bitwise_or.reduceat(cur[nbr], starts)
+            fresh = f & ~seen
+            if not fresh.any():
+                break
+            seen |= fresh
+            block[((fresh[None, :] >> shifts[:nbits]) & np.uint64(1)).astype(bool)] = level
+            cur = fresh
+    return out
+
+
+class GraphDistances:
+    """Hop distances of one graph, computed on demand a block of source rows at a time.
+
+    rowptr / cols: the symmetric CSR of graph_csr (tensors or ndarrays); `device`: where the CSR and every result live (default:
+    the CSR's own device).  On a GPU the rows come from the HIP kernel behind ops.graph_hop_rows, on the CPU from host_hop_rows.
+    No call holds more than one block of rows: at most max_block_bytes of int32 [R, N] (R a multiple of 64, at least 64) plus
+    the kernel's workspace of 24 N bytes per 64 rows."""
+
+    def __init__(self, rowptr, cols, device=None, max_block_bytes=128 << 20):
+        rowptr, cols = torch.as_tensor(rowptr), torch.as_tensor(cols)
+        self.device = torch.device(device) if device is not None else rowptr.device
+        self.rowptr = rowptr.to(device=self.device, dtype=torch.int64).contiguous()
+        self.cols = cols.to(device=self.device, dtype=torch.int32).contiguous()
+        self.num_nodes = self.rowptr.numel() - 1
+        if self.num_nodes <= 0:
+            raise ValueError("the graph has no nodes")
+        self.max_block_bytes = int(max_block_bytes)
+        self.block_rows = self.rows_per_block(self.max_block_bytes)
+        self._buf = None
+        self._ws = None
+
+    def rows_per_block(self, max_block_bytes):
+        """Source rows per block for a byte budget: whole words of 64 sources, at least one, at most the graph."""
+        R = max(64, (int(max_block_bytes) // (4 * self.num_nodes)) // 64 * 64)
+        return min(R, -(-self.num_nodes // 64) * 64)
+
+    def workspace_bytes(self, count=None):
+        """Bytes of kernel workspace behind a block of `count` rows (default: a full block): 24 N per word of 64 sources."""
+        count = self.block_rows if count is None else int(count)
+        return -(-count // 64) * 24 * self.num_nodes
+
+    def rows(self, begin, count, out=None):
+        """int32 [count, N]: hops from the sources [begin, begin + count); 0 on the diagonal, -1 for unreachable nodes.  `out`
+        (int32 [>= count, N] on the device) is written and its first `count` rows returned."""
+        begin, count = int(begin), int(count)
+        N = self.num_nodes
+        if begin < 0 or count < 0 or begin + count > N:
+            raise ValueError(f"source block [{begin}, {begin + count}) outside [0, {N})")
+        if self.device.type != "cuda":
+            got = torch.from_numpy(host_hop_rows(self.rowptr, self.cols, begin, count))
+            if out is None:
+                return got
+            out[:count].copy_(got)
+            return out[:count]
+        from sympa_amd import ops
+        need = self.workspace_bytes(count)
+        if self._ws is None or self._ws.numel() * 8 < need:
+            self._ws = None
+            self._ws = torch.empty(max(need, self.workspace_bytes(min(self.block_rows, N))) // 8, dtype=torch.int64,
+                                   device=self.device)
+        return ops.graph_hop_rows(self.rowptr, self.cols, begin, count, out=out, workspace=self._ws)
+
+    def _block_buffer(self):
+        if self._buf is None:
+            self._buf = torch.empty(min(self.block_rows, self.num_nodes), self.num_nodes, dtype=torch.int32, device=self.device)
+        return self._buf
+
+    def release(self):
+        """Frees the reused row block and the kernel workspace."""
+        self._buf = self._ws = None
+
+    def blocks(self, begin=0, count=None):
+        """Yields (first row, int32 [r, N] rows) over [begin, begin + count) through ONE reused buffer: consume a block before
+        taking the next."""
+        N = self.num_nodes
+        count = N - begin if count is None else int(count)
+        buf = self._block_buffer()
+        R = buf.shape[0]
+        for b in range(begin, begin + count, R):
+            r = min(R, begin + count - b)
+            yield b, self.rows(b, r, out=buf)
+
+    def pairs(self, src_dst_ids):
+        """fp64 [b] hop distances of the pairs src_dst_ids[:, :2] (any order, any device), `inf` for unreachable pairs.  The pairs
+        are grouped by the block of their source; every block that is needed is computed once and gathered from."""
+        ids = torch.as_tensor(src_dst_ids)
+        if ids.dim() != 2 or ids.shape[1] < 2:
+            raise ValueError(f"src_dst_ids must be [b, >=2], got {tuple(ids.shape)}")
+        ids = ids[:, :2].to(device=self.device, dtype=torch.int64)
+        N = self.num_nodes
+        out = torch.empty(ids.shape[0], dtype=torch.float64, device=self.device)
+        if ids.shape[0] == 0:
+            return out
+        if int(ids.min()) < 0 or int(ids.max()) >= N:
+            raise IndexError(f"a node id is outside [0, {N})")
+        buf = self._block_buffer()
+        R = buf.shape[0]
+        order = torch.argsort(ids[:, 0], stable=True)
+        src, dst = ids[order, 0], ids[order, 1]
+        blk = src // R
+        needed, counts = torch.unique_consecutive(blk, return_counts=True)
+        ends = torch.cumsum(counts, 0).tolist()
+        start = 0
+        for k, end in zip(needed.tolist(), ends):
+            b = k * R
+            rows = self.rows(b, min(R, N - b), out=buf)
+            h = rows[src[start:end] - b, dst[start:end]].to(torch.float64)
+            out[order[start:end]] = torch.where(h < 0, torch.full_like(h, float("inf")), h)
+            start = end
+        return out
+
+    def count_triplets(self):
+        """Number of pairs i < j with 0 < hops < inf (one pass over every row block)."""
+        total = torch.zeros((), dtype=torch.int64, device=self.device)
+        col = torch.arange(self.num_nodes, device=self.device)
+        for b, rows in self.blocks():
+            i = torch.arange(b, b + rows.shape[0], device=self.device)
+            total += ((rows > 0) & (col[None, :] > i[:, None])).sum()
+        return int(total)
+
+    def triplets(self, max_bytes=TRIPLETS_MAX_BYTES):
+        """int64 [T, 3] on the device: every (i, j, hops) with i < j and 0 < hops < inf in lexicographic order, element for
+        element what data.graph_triplets returns, built block by block.  Raises MemoryError when the upper bound N (N - 1) / 2
+        on T exceeds max_bytes / 24 and the counted T does too (the 45 500-node product graph has 1.035e9 triplets, 24.8 GB:
+        use rows / pairs / Model.evaluate_all_pairs there)."""
+        N = self.num_nodes
+        if N * (N - 1) // 2 * 24 > max_bytes:
+            T = self.count_triplets()
+            if T * 24 > max_bytes:
+                raise MemoryError(f"{T} triplets need {T * 24} bytes, above the budget of {int(max_bytes)} bytes: stream the rows "
+                                  "(GraphDistances.rows / pairs, Model.evaluate_all_pairs) instead of materialising them")
+        col = torch.arange(N, device=self.device)
+        parts = []
+        for b, rows in self.blocks():
+            i = torch.arange(b, b + rows.shape[0], device=self.device)
+            r, j = torch.nonzero((rows > 0) & (col[None, :] > i[:, None]), as_tuple=True)      # row-major: lexicographic
+            parts.append(torch.stack((r + b, j, rows[r, j].to(torch.int64)), 1))
+        return torch.cat(parts) if parts else torch.zeros(0, 3, dtype=torch.int64, device=self.device)
+
+    def neighbor_csr(self):
+        """(rowptr int64 [N + 1], cols int32 [E]) of the hop-1 neighbour sets, rows ascending and unique: what ops.map_rows and
+        MeanAveragePrecisionMetric.from_csr take, equal to ops.neighbor_csr over this graph's triplets."""
+        N = self.num_nodes
+        deg = self.rowptr[1:] - self.rowptr[:-1]
+        rows = torch.repeat_interleave(torch.arange(N, device=self.device), deg)
+        cols = self.cols.to(torch.int64)
+        keep = (cols >= 0) & (cols < N) & (cols != rows)
+        key = torch.unique(rows[keep] * N + cols[keep])
+        r = key // N
+        rowptr = torch.zeros(N + 1, dtype=torch.int64, device=self.device)
+        rowptr[1:] = torch.cumsum(torch.bincount(r, minlength=N), 0)
+        return rowptr, (key - r * N).to(torch.int32)

@@ -80,6 +80,19 @@ class MeanAveragePrecisionMetric:
         self._neighbors = None
         self._csr = {}
 
+    @classmethod
+    def from_csr(cls, rowptr, cols):
+        """The metric over neighbour sets that already are a CSR (rowptr int64 [N + 1], cols int32 [E], rows ascending and
+        unique: sympa_amd.graph.GraphDistances.neighbor_csr), for graphs whose triples are too many to list."""
+        self = cls.__new__(cls)
+        self.rowptr, self.cols = rowptr.to(torch.int64), cols.to(torch.int32)
+        self.num_nodes = self.rowptr.numel() - 1
+        deg = self.rowptr[1:] - self.rowptr[:-1]
+        self.max_degree = int(deg.max()) if deg.numel() else 0
+        self._neighbors = None
+        self._csr = {}
+        return self
+
     @property
     def neighbors(self):
         """The reference's defaultdict(set) {node: set of neighbours}, built on first access."""

@@ -384,6 +384,60 @@ class Model(nn.Module):
         value = float(ap.mean())
         return (value, ap) if return_rows else value
 
+    def evaluate_all_pairs(self, graph_distances, max_block_bytes=128 << 20, group=None):
+        """Extension: the average distortion |d_manifold - d_graph| / d_graph (metrics.py:21) over ALL reachable pairs i < j of a
+        graph, without its triplets: what evaluate() returns over data.graph_triplets, for graphs whose triplets cannot be listed.
+        `graph_distances`: a sympa_amd.graph.GraphDistances on the table's device.  Row blocks of the distance matrix (the kernels
+        behind distance_matrix(row_begin, row_count)) and of GraphDistances.rows stream through one reused pair of [R, N] buffers,
+        fp64 and int32, R from max_block_bytes over both (12 N bytes per row, whole words of 64 rows); each block is reduced on the
+        device to per-row sums and pair counts (ops.graph_distortion_rows: a row's sum depends on the row alone), so the value does
+        not depend on the block size.  With `group` set or a default process group initialised every rank takes its contiguous
+        share of the rows and the zero-padded [N] vectors are combined by an exact all-reduce: bitwise the single-process value.
+        One host sync (the returned float)."""
+        from sympa_amd import distributed as sd
+        man = self.manifold
+        table = self.embeddings.embeds.detach()
+        dev = table.device
+        ops._need_gpu(table, "embedding table")
+        N = table.shape[0]
+        gd = graph_distances
+        if gd.num_nodes != N:
+            raise ValueError(f"the graph has {gd.num_nodes} nodes but the table {N} rows")
+        if gd.device != dev:
+            raise ValueError(f"the graph distances live on {gd.device}, the table on {dev}")
+        spd = man.model_name == "spd"
+        row_bytes = (4 + 8 + (32 if spd else 0)) * N          # spd: + the [N, 2] pair list and the arange repeats behind it
+        R = max(64, (int(max_block_bytes) // row_bytes) // 64 * 64)
+        begin, count = (0, N) if group is None and not sd.dist.is_initialized() else sd.row_shard(N, group)
+        R = min(R, max(count, 1))
+        sums = torch.zeros(N, dtype=torch.float64, device=dev)
+        pairs = torch.zeros(N, dtype=torch.int64, device=dev)
+        if count > 0:
+            hbuf = torch.empty(R, N, dtype=torch.int32, device=dev)
+            if not spd:
+                weights = man.metric.weights if man.metric.kind is MetricType.WEIGHTED_SUM else None
+                need = ops._lib.load().sympa_all_pairs_workspace_bytes(N, table.shape[-1], ops.MODEL_IDS[man.model_name])
+                ws = torch.empty(need // 8, dtype=torch.float64, device=dev) if need > 0 else None
+                dbuf = torch.empty(R, N, dtype=torch.float64, device=dev)
+        with torch.no_grad():
+            for b in range(begin, begin + count, R):
+                r = min(R, begin + count - b)
+                if spd:
+                    rows = self.distance_matrix(b, r)
+                else:
+                    rows = ops.all_pairs_dist(table, man.model_name, man.metric.kind.value, weights, self.scale.detach(),
+                                              self.scale_coef, b, r, out=dbuf[:r], packed=need > 0, workspace=ws,
+                                              flags=ops.FLAG_NO_SYMMETRY)
+                hops = gd.rows(b, r, out=hbuf)
+                ops.graph_distortion_rows(rows, hops, b, row_sum=sums[b:b + r], row_pairs=pairs[b:b + r])
+        if group is not None or sd.dist.is_initialized():
+            sd.allreduce_row_shards(sums, group)
+            sd.allreduce_row_shards(pairs, group)
+        total = torch.stack((sums.sum(), pairs.sum().to(torch.float64))).tolist()
+        if total[1] == 0:
+            raise ValueError("evaluate_all_pairs() over a graph without a reachable pair (statistics.mean raises in the reference too)")
+        return total[0] / total[1]
+
     def distance(self, src_embeds, dst_embeds):   # model.py:32-38
         return self.manifold.dist(src_embeds, dst_embeds)
 

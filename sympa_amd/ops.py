@@ -1577,3 +1577,76 @@ def map_rows(dist_rows, row_begin, neighbors, float32=False, out=None, workspace
     if _debug:
         check_status(dev)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# Graph hop distances (C-ABI sympa_graph_hop_rows; reference preprocess.py:101-126) and the distortion of distance rows
+# against them (C-ABI sympa_graph_distortion_rows; metrics.py:21)
+# ---------------------------------------------------------------------------------------------------
+def graph_hops_workspace_bytes(num_nodes, src_count):
+    return int(_lib.load().sympa_graph_hops_workspace_bytes(int(num_nodes), int(src_count)))
+
+
+def graph_hop_rows(rowptr, cols, src_begin, src_count, out=None, workspace=None):
+    """Hop distances from the sources [src_begin, src_begin + src_count) to every node (C-ABI sympa_graph_hop_rows) on the
+    current stream.  rowptr int64 [N + 1], cols int32 [E]: a symmetric CSR on the device, self-loops and duplicates removed
+    (sympa_amd.graph.graph_csr).  Returns out int32 [src_count, N]: 0 on the diagonal, -1 for unreachable nodes; every element is
+    written.  workspace: a device tensor of at least graph_hops_workspace_bytes(N, src_count) bytes (allocated when not given).
+    A column outside [0, N) is skipped and raises IndexError from check_status()."""
+    lib = _lib.load()
+    _need_gpu(rowptr, "rowptr")
+    _need_gpu(cols, "cols")
+    dev = rowptr.device
+    if cols.device != dev or rowptr.dtype != torch.int64 or cols.dtype != torch.int32 or rowptr.dim() != 1 or cols.dim() != 1:
+        raise ValueError("the CSR must be (int64 rowptr [N + 1], int32 cols [E]) on one device")
+    rowptr, cols = rowptr.contiguous(), cols.contiguous()
+    N = rowptr.numel() - 1
+    src_begin, src_count = int(src_begin), int(src_count)
+    if out is None:
+        out = torch.empty(max(src_count, 0), max(N, 0), dtype=torch.int32, device=dev)
+    elif out.dtype != torch.int32 or out.device != dev or out.dim() != 2 or out.shape[0] < src_count or out.shape[1] != N or \
+            out.stride(1) != 1 or (out.shape[0] > 1 and out.stride(0) < N):
+        raise ValueError(f"out must be an int32 [>= {src_count}, {N}] tensor with unit column stride on the CSR's device")
+    need = lib.sympa_graph_hops_workspace_bytes(N, src_count)
+    if workspace is None:
+        workspace = torch.empty(max(need // 8, 1), dtype=torch.int64, device=dev)
+    elif workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError("workspace must be a contiguous tensor on the CSR's device")
+    stride = out.stride(0) if out.shape[0] > 1 else N
+    st = _status_buf(dev)
+    with torch.cuda.device(dev):
+        rc = lib.sympa_graph_hop_rows(rowptr.data_ptr(), cols.data_ptr() if cols.numel() else None, N, cols.numel(), src_begin,
+                                      src_count, out.data_ptr(), stride, workspace.data_ptr(),
+                                      workspace.numel() * workspace.element_size(), st.data_ptr(), _stream())
+    _lib.check(rc)
+    if _debug:
+        check_status(dev)
+    return out[:src_count]
+
+
+def graph_distortion_rows(dist_rows, hop_rows, row_begin, row_sum=None, row_pairs=None):
+    """Per-row distortion sums of rows [row_begin, row_begin + R) (C-ABI sympa_graph_distortion_rows): row_sum[r] = sum over the
+    columns j > row_begin + r with hop_rows[r, j] > 0 of |dist_rows[r, j] - hops| / hops, row_pairs[r] their number.  dist_rows
+    fp64 [R, N], hop_rows int32 [R, N] (graph_hop_rows), unit column strides.  Returns (row_sum fp64 [R], row_pairs int64 [R])."""
+    lib = _lib.load()
+    _need_gpu(dist_rows, "dist_rows")
+    _need_gpu(hop_rows, "hop_rows")
+    dev = dist_rows.device
+    if dist_rows.dtype != torch.float64 or hop_rows.dtype != torch.int32 or dist_rows.dim() != 2 or \
+            dist_rows.shape != hop_rows.shape or hop_rows.device != dev or dist_rows.stride(1) != 1 or hop_rows.stride(1) != 1:
+        raise ValueError("dist_rows (float64) and hop_rows (int32) must be [R, N] tensors of one shape and device with unit "
+                         "column stride")
+    R, N = dist_rows.shape
+    if row_sum is None:
+        row_sum = torch.empty(R, dtype=torch.float64, device=dev)
+    if row_pairs is None:
+        row_pairs = torch.empty(R, dtype=torch.int64, device=dev)
+    for t, dt, name in ((row_sum, torch.float64, "row_sum"), (row_pairs, torch.int64, "row_pairs")):
+        if t.dtype != dt or t.device != dev or t.numel() != R or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} [R] tensor on the rows' device")
+    with torch.cuda.device(dev):
+        rc = lib.sympa_graph_distortion_rows(dist_rows.data_ptr(), dist_rows.stride(0) if R > 1 else N, hop_rows.data_ptr(),
+                                             hop_rows.stride(0) if R > 1 else N, int(row_begin), R, N, row_sum.data_ptr(),
+                                             row_pairs.data_ptr(), _stream())
+    _lib.check(rc)
+    return row_sum, row_pairs

@@ -3,6 +3,7 @@
 rewrite of them: SURVEY 8f): graph -> triplets -> Model -> fused training step -> RiemannianSGD -> distortion.
 
     python tools/train_siegel.py --graph grid3d-125 --manifold upper --metric riem --dims 2 --epochs 50
+    python tools/train_siegel.py --graph product-cartesian-45500 --dims 8 --sampled-pairs 1048576 --batch_size 262144
 
 Per batch it runs exactly two kernels: sympa_model_loss_backward (forward + AverageDistortionLoss + backward +
 scatter, runner.py:101-105) and sympa_rsgd_step (geoopt RiemannianSGD, train.py:66-68), plus the gradient clip
@@ -42,15 +43,25 @@ def train(args, log=print):
     if world > 1 and not dist.is_initialized():
         dist.init_process_group("nccl", device_id=dev)
     torch.manual_seed(args.seed)
-    trip, id2node = data.graph_triplets(data.named_graph(args.graph))
+    hops = None
+    if getattr(args, "sampled_pairs", 0):
+        # graphs whose triplets cannot be listed (product-cartesian-45500: 1.035e9): every epoch draws fresh pairs and labels
+        # them with their hop distances on the device; the evaluation streams all pairs in row blocks
+        from sympa_amd.graph import GraphDistances, graph_csr
+        rowptr, cols, id2node = graph_csr(data.named_graph(args.graph))
+        hops = GraphDistances(rowptr, cols, device=dev)
+        trip = None
+    else:
+        trip, id2node = data.graph_triplets(data.named_graph(args.graph))
     args.num_points = len(id2node)
     model = Model(args).to(dev)
     if args.optim == "radam":        # train.py:69-70
         opt = RiemannianAdam(model.parameters(), lr=args.learning_rate * world, eps=1e-7, stabilize=None)
     else:                            # train.py:66-68
         opt = RiemannianSGD(model.parameters(), lr=args.learning_rate * world, weight_decay=0.0, stabilize=None)
-    ids_all = trip[:, :2].contiguous().to(dev)
-    gd_all = trip[:, 2].to(torch.float64).to(dev)
+    if hops is None:
+        ids_all = trip[:, :2].contiguous().to(dev)
+        gd_all = trip[:, 2].to(torch.float64).to(dev)
     batch = max(1, args.batch_size // world)
     history = []
     # single GPU: the whole step is one hipGraph replay
@@ -86,7 +97,14 @@ def train(args, log=print):
         else:
             stepper = None
     for epoch in range(1, args.epochs + 1):
-        mine = shard_triplets(trip, rank, world, epoch=epoch, seed=0).to(dev)
+        if hops is not None:
+            per_rank = max(1, args.sampled_pairs // world)
+            ids = data.sample_pairs(args.num_points, per_rank, batch_id=(epoch - 1) * world + rank, seed=args.seed).to(dev)
+            d = hops.pairs(ids)
+            keep = torch.isfinite(d)                      # a pair across two components has no distance to learn
+            mine = torch.cat((ids[keep], d[keep].to(torch.int64)[:, None]), 1)
+        else:
+            mine = shard_triplets(trip, rank, world, epoch=epoch, seed=0).to(dev)
         # inside every batch: pairs with the same source row adjacent (free for SGD) -- load_epoch of the replayed steps sorts
         # by itself; only the eager per-batch loop needs it here (one argsort per epoch, not two)
         loads_epoch = dstep is not None or (graphed is not None and graphed.mode == "two_kernels")
@@ -146,7 +164,7 @@ def train(args, log=print):
         if epoch % args.val_every == 0 or epoch == args.epochs:
             torch.cuda.synchronize(dev)
             t_train = time.perf_counter() - t0
-            distortion = evaluate(model, ids_all, gd_all, args.batch_size)
+            distortion = model.evaluate_all_pairs(hops) if hops is not None else evaluate(model, ids_all, gd_all, args.batch_size)
             ops.check_status(dev)
             history.append((epoch, float(loss_sum) / max(1, mine.shape[0]), distortion))
             if rank == 0:
@@ -173,6 +191,11 @@ def parser():
     ap.add_argument("--burnin", type=int, default=10)
     ap.add_argument("--val_every", type=int, default=5)
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--sampled-pairs", dest="sampled_pairs", type=int, default=0, metavar="B",
+                    help="train on B freshly sampled pairs per epoch (data.sample_pairs), labelled with hop distances computed "
+                         "on the device (sympa_amd.graph.GraphDistances.pairs), instead of on the list of all triplets; the "
+                         "distortion is then taken over all pairs in row blocks (Model.evaluate_all_pairs).  With --graph "
+                         "product-cartesian-45500 this trains configs[3] on its own graph")
     ap.add_argument("--grad_exchange", default="none", choices=["none", "auto", "dense", "rows", "sharded"],
                     help="single GPU: run the step through sympa_amd.distributed.GradientExchange anyway (tests); with "
                          "N > 1 GPUs the exchange is always on and this picks its mode (none = auto)")
