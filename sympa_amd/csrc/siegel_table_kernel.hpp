@@ -84,41 +84,7 @@ SYMPA_UNROLL
 //     x <- projx(x - lr (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps_adam))
 // pows: device words {b1^t, b2^t} (already advanced to this step by the caller): no host state in the kernel's arguments
 // changes from step to step, so the launch can sit in a replayed hipGraph.
-// The row update itself.  In: x = the point, g = the (clipped) Euclidean gradient row.  Out: x = the new point, g = the new
-// first moment, returns the new second moment through vn; `moved` = projx changed the point.
-template <int N, int MODEL>
-__device__ __forceinline__ bool radam_row_update(sympa::CMat<N>& x, sympa::CMat<N>& g, const double* __restrict__ m_row,
-                                                 const double v_old, double& vn, double lr, double b1, double b2,
-                                                 double eps_adam, double wd, double pow1, double pow2, double eps, int& st) {
-    sympa::CMat<N> r;
-    if (wd != 0.0) {
-SYMPA_UNROLL
-        for (int a = 0; a < N; ++a)
-SYMPA_UNROLL
-            for (int c = 0; c < N; ++c) {
-                g.re[a][c] = sympa::d_fma(wd, x.re[a][c], g.re[a][c]);
-                g.im[a][c] = sympa::d_fma(wd, x.im[a][c], g.im[a][c]);
-            }
-    }
-    sympa::egrad2rgrad<N, MODEL>(x, g, r);
-    const double s = sympa::tangent_sqnorm<N, MODEL>(x, r, st);
-    vn = sympa::d_fma(b2, v_old, (1.0 - b2) * s);
-    const double bc1 = 1.0 - pow1, bc2 = 1.0 - pow2;
-    const double step = lr / (bc1 * (sqrt(vn / bc2) + eps_adam));
-    // m <- b1 m + (1 - b1) r (kept in g), x <- x - step m
-    sympa::load_full<N>(m_row, g);
-SYMPA_UNROLL
-    for (int a = 0; a < N; ++a)
-SYMPA_UNROLL
-        for (int c = 0; c < N; ++c) {
-            g.re[a][c] = sympa::d_fma(b1, g.re[a][c], (1.0 - b1) * r.re[a][c]);
-            g.im[a][c] = sympa::d_fma(b1, g.im[a][c], (1.0 - b1) * r.im[a][c]);
-            x.re[a][c] = sympa::d_fma(-step, g.re[a][c], x.re[a][c]);
-            x.im[a][c] = sympa::d_fma(-step, g.im[a][c], x.im[a][c]);
-        }
-    return sympa::projx<N, MODEL>(x, eps, st);
-}
-
+// The row update itself is sympa::radam_row_update (siegel_table_math.hpp), shared with the CPU build of the tests.
 template <int N, int MODEL>
 __global__ __launch_bounds__(BLOCK) void radam_row_kernel(double* z, const double* grad, double* m, double* v, int64_t b,
                                                           double lr, double b1, double b2, double eps_adam, double wd,
@@ -133,7 +99,7 @@ __global__ __launch_bounds__(BLOCK) void radam_row_kernel(double* z, const doubl
     sympa::load_full<N>(grad + ii * ROW, g);
     int st = 0;
     double vn;
-    const bool moved = radam_row_update<N, MODEL>(x, g, m + ii * ROW, v[ii], vn, lr, b1, b2, eps_adam, wd, pows[0], pows[1], eps, st);
+    const bool moved = sympa::radam_row_update<N, MODEL>(x, g, m + ii * ROW, v[ii], vn, lr, b1, b2, eps_adam, wd, pows[0], pows[1], eps, st);
     if (live) {
         sympa::store_full<N>(m + i * ROW, g);
         v[i] = vn;
@@ -306,7 +272,7 @@ SYMPA_UNROLL
         pow1 = a.apows[0] * a.b1;
         pow2 = a.apows[1] * a.b2;
         double vn;
-        moved = radam_row_update<N, MODEL>(z, g, a.am + ii * ROW, a.av[ii], vn, a.lr, a.b1, a.b2, a.aeps, a.wd, pow1, pow2, a.eps, st);
+        moved = sympa::radam_row_update<N, MODEL>(z, g, a.am + ii * ROW, a.av[ii], vn, a.lr, a.b1, a.b2, a.aeps, a.wd, pow1, pow2, a.eps, st);
         if (live) {
             sympa::store_full<N>(a.am + i * ROW, g);
             a.av[i] = vn;

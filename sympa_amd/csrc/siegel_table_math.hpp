@@ -201,8 +201,12 @@ SYMPA_UNROLL
             }
         return true;
     } else {
-        // Takagi values of Z = sqrt(eig(Z^H Z)); clamp sigma_k > 1 - eps:
-        //   Z~ = Z - sum_k (sigma_k - (1 - eps)) e^{i theta_k} conj(u_k) u_k^H,   e^{i theta_k} = u_k^T Z u_k / sigma_k
+        // Takagi values of Z = sqrt(eig(H)), H = Z^H Z = V diag(lambda) V^H; clamp sigma_k > 1 - eps:
+        //   Z~ = Z g(H),  g(lambda) = min(1, (1 - eps) / sqrt(lambda))
+        //      = Z - sum_k f_k (Z u_k) u_k^H,   f_k = (sigma_k - (1 - eps)) / sigma_k over the clamped k
+        // A matrix function of H: the same for ANY orthonormal eigenbasis, so the arbitrary basis the Jacobi returns inside a
+        // cluster of Takagi values does not matter (a clamp written per Takagi vector, conj(u_k) u_k^H scaled by u_k^T Z u_k,
+        // drops the cross terms u_j^T Z u_k there and leaves the row outside the domain).
         Herm<N> h;
         gram<N>(z, h);
         CMat<N> v;
@@ -218,26 +222,17 @@ SYMPA_UNROLL
         for (int k = 0; k < N; ++k) {
             const double sig = d_sqrt(fmax(h.d[k], 0.0));
             if (!(sig > lim)) continue;
-            double pr = 0.0, pi = 0.0;            // u_k^T (Z u_k)
+            const double f = (sig - lim) * d_rcp(sig);
 SYMPA_UNROLL
             for (int i = 0; i < N; ++i) {
-                pr = d_fma(v.re[i][k], zu.re[i][k], pr);
-                pr = d_fma(-v.im[i][k], zu.im[i][k], pr);
-                pi = d_fma(v.re[i][k], zu.im[i][k], pi);
-                pi = d_fma(v.im[i][k], zu.re[i][k], pi);
-            }
-            const double f = (sig - lim) * d_rcp(sig);          // (sigma - lim) e^{i theta} = f * p,  p = sigma e^{i theta}
-            const double fr = f * pr, fi = f * pi;
-SYMPA_UNROLL
-            for (int i = 0; i < N; ++i)
+                const double fr = f * zu.re[i][k], fi = f * zu.im[i][k];
 SYMPA_UNROLL
                 for (int j = 0; j < N; ++j) {
-                    // conj(u_ik) conj(u_jk)   (conj(u_k) u_k^H)_ij
-                    const double cr = v.re[i][k] * v.re[j][k] - v.im[i][k] * v.im[j][k];
-                    const double ci = -(v.re[i][k] * v.im[j][k] + v.im[i][k] * v.re[j][k]);
-                    z.re[i][j] -= fr * cr - fi * ci;
-                    z.im[i][j] -= fr * ci + fi * cr;
+                    // f (Z u_k)_i conj(u_jk)
+                    z.re[i][j] -= d_fma(fr, v.re[j][k], fi * v.im[j][k]);
+                    z.im[i][j] -= d_fma(fi, v.re[j][k], -(fr * v.im[j][k]));
                 }
+            }
         }
         symmetrise<N>(z);
         return true;
@@ -321,6 +316,44 @@ SYMPA_UNROLL
     for (int i = 0; i < N; ++i)
 SYMPA_UNROLL
         for (int j = 0; j < N; ++j) { p[i * N + j] = z.re[i][j]; p[N * N + i * N + j] = z.im[i][j]; }
+}
+
+// ---- one RiemannianAdam step on one row (the kernels: siegel_table_kernel.hpp) ------------------------------------
+//     g <- egrad2rgrad(x, grad + wd x);  m <- b1 m + (1 - b1) g;  v <- b2 v + (1 - b2) inner(x, g, g)   (one v per row);
+//     x <- projx(x - lr (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps_adam)),   pow1 = b1^t, pow2 = b2^t
+// In: x = the point, g = the (clipped) Euclidean gradient row.  Out: x = the new point, g = the new
+// first moment, returns the new second moment through vn; `moved` = projx changed the point.
+template <int N, int MODEL>
+SYMPA_HD bool radam_row_update(CMat<N>& x, CMat<N>& g, const double* __restrict__ m_row,
+                                                 const double v_old, double& vn, double lr, double b1, double b2,
+                                                 double eps_adam, double wd, double pow1, double pow2, double eps, int& st) {
+    CMat<N> r;
+    if (wd != 0.0) {
+SYMPA_UNROLL
+        for (int a = 0; a < N; ++a)
+SYMPA_UNROLL
+            for (int c = 0; c < N; ++c) {
+                g.re[a][c] = d_fma(wd, x.re[a][c], g.re[a][c]);
+                g.im[a][c] = d_fma(wd, x.im[a][c], g.im[a][c]);
+            }
+    }
+    egrad2rgrad<N, MODEL>(x, g, r);
+    const double s = tangent_sqnorm<N, MODEL>(x, r, st);
+    vn = d_fma(b2, v_old, (1.0 - b2) * s);
+    const double bc1 = 1.0 - pow1, bc2 = 1.0 - pow2;
+    const double step = lr / (bc1 * (sqrt(vn / bc2) + eps_adam));
+    // m <- b1 m + (1 - b1) r (kept in g), x <- x - step m
+    load_full<N>(m_row, g);
+SYMPA_UNROLL
+    for (int a = 0; a < N; ++a)
+SYMPA_UNROLL
+        for (int c = 0; c < N; ++c) {
+            g.re[a][c] = d_fma(b1, g.re[a][c], (1.0 - b1) * r.re[a][c]);
+            g.im[a][c] = d_fma(b1, g.im[a][c], (1.0 - b1) * r.im[a][c]);
+            x.re[a][c] = d_fma(-step, g.re[a][c], x.re[a][c]);
+            x.im[a][c] = d_fma(-step, g.im[a][c], x.im[a][c]);
+        }
+    return projx<N, MODEL>(x, eps, st);
 }
 
 }  // namespace sympa

@@ -152,22 +152,39 @@ def hostsim_dist_bwd_split(z1, z2, go, model, metric, weights=None, eps=1e-5):
 
 
 def hostsim_table(op, model, z, g=None, lr=0.0, wd=0.0, eps=1e-5):
-    """op: 'projx' | 'rsgd' | 'egrad2rgrad' -> (rows, projected_count)"""
+    """op: 'projx' | 'rsgd' | 'egrad2rgrad' -> (rows, projected_count);  'tangent_sqnorm' (g = the tangent) -> (inner [b], 0)"""
     lib = hostsim()
     P = ctypes.c_void_p
     z = np.ascontiguousarray(z, dtype=np.float64)
     b, _, n, _ = z.shape
-    out = np.zeros_like(z)
+    out = np.zeros(b) if op == "tangent_sqnorm" else np.zeros_like(z)
     gp = None
     if g is not None:
         g = np.ascontiguousarray(g, dtype=np.float64)
         gp = P(g.ctypes.data)
     moved = ctypes.c_int32(0)
-    st = lib.sympa_hostsim_table({"projx": 0, "rsgd": 1, "egrad2rgrad": 2}[op], MODELS.index(model), n, P(z.ctypes.data),
-                                 gp, P(out.ctypes.data), ctypes.c_int64(b), ctypes.c_double(lr), ctypes.c_double(wd),
-                                 ctypes.c_double(eps), ctypes.byref(moved))
+    st = lib.sympa_hostsim_table({"projx": 0, "rsgd": 1, "egrad2rgrad": 2, "tangent_sqnorm": 3}[op], MODELS.index(model), n,
+                                 P(z.ctypes.data), gp, P(out.ctypes.data), ctypes.c_int64(b), ctypes.c_double(lr),
+                                 ctypes.c_double(wd), ctypes.c_double(eps), ctypes.byref(moved))
     assert st == 0, st
     return out, moved.value
+
+
+def hostsim_radam(model, x, g, exp_avg, exp_avg_sq, pows, lr, betas, eps_adam, wd, eps=1e-5):
+    """One RiemannianAdam step by the fused kernels' row function (pows = beta^t of this step) -> (rows, exp_avg, exp_avg_sq,
+    projected_count); the inputs are left alone."""
+    lib = hostsim()
+    P, D = ctypes.c_void_p, ctypes.c_double
+    x, m = (np.array(a, dtype=np.float64, order="C") for a in (x, exp_avg))
+    v = np.array(exp_avg_sq, dtype=np.float64, order="C")
+    g = np.ascontiguousarray(g, dtype=np.float64)
+    b, _, n, _ = x.shape
+    moved = ctypes.c_int32(0)
+    st = lib.sympa_hostsim_radam(MODELS.index(model), n, P(x.ctypes.data), P(g.ctypes.data), P(m.ctypes.data), P(v.ctypes.data),
+                                 ctypes.c_int64(b), D(lr), D(betas[0]), D(betas[1]), D(eps_adam), D(wd), D(pows[0]), D(pows[1]),
+                                 D(eps), ctypes.byref(moved))
+    assert st == 0, st
+    return x, m, v, moved.value
 
 
 def spd_points(b, n, s, g):

@@ -323,6 +323,9 @@ int run_table(int op, int model, const double* z, const double* g, double* out, 
         if (op == 2) {
             if (model == 0) sympa::egrad2rgrad<N, sympa::MODEL_UPPER>(a, gg, r); else sympa::egrad2rgrad<N, sympa::MODEL_BOUNDED>(a, gg, r);
             sympa::store_full<N>(out + i * 2 * N * N, r);
+        } else if (op == 3) {      // inner(z, g, g): one value per row; the point through its upper triangle like the kernel's load
+            sympa::load_point<N>(z + i * 2 * N * N, a);
+            out[i] = (model == 0) ? sympa::tangent_sqnorm<N, sympa::MODEL_UPPER>(a, gg, st) : sympa::tangent_sqnorm<N, sympa::MODEL_BOUNDED>(a, gg, st);
         } else {
             bool m;
             if (op == 0) m = (model == 0) ? sympa::projx<N, sympa::MODEL_UPPER>(a, eps, st) : sympa::projx<N, sympa::MODEL_BOUNDED>(a, eps, st);
@@ -336,7 +339,7 @@ int run_table(int op, int model, const double* z, const double* g, double* out, 
 }
 }  // namespace
 
-// op: 0 projx, 1 rsgd step (out = new rows), 2 egrad2rgrad
+// op: 0 projx, 1 rsgd step (out = new rows), 2 egrad2rgrad, 3 tangent_sqnorm (g = the tangent, out = [b])
 extern "C" int sympa_hostsim_table(int op, int model, int n, const double* z, const double* g, double* out, int64_t b,
                                    double lr, double wd, double eps, int32_t* projected) {
     switch (n) {
@@ -348,6 +351,48 @@ extern "C" int sympa_hostsim_table(int op, int model, int n, const double* z, co
         case 6: return run_table<6>(op, model, z, g, out, b, lr, wd, eps, projected);
         case 7: return run_table<7>(op, model, z, g, out, b, lr, wd, eps, projected);
         case 8: return run_table<8>(op, model, z, g, out, b, lr, wd, eps, projected);
+        default: return -2;
+    }
+}
+
+namespace {
+template <int N>
+int run_radam(int model, double* z, const double* g, double* m, double* v, int64_t b, double lr, double b1, double b2,
+              double eps_adam, double wd, double pow1, double pow2, double eps, int32_t* projected) {
+    int st = 0, moved = 0;
+    constexpr int64_t ROW = 2 * N * N;
+    for (int64_t i = 0; i < b; ++i) {
+        sympa::CMat<N> x, gg;
+        sympa::load_full<N>(z + i * ROW, x);
+        sympa::load_full<N>(g + i * ROW, gg);
+        double vn;
+        const bool mv = (model == 0)
+            ? sympa::radam_row_update<N, sympa::MODEL_UPPER>(x, gg, m + i * ROW, v[i], vn, lr, b1, b2, eps_adam, wd, pow1, pow2, eps, st)
+            : sympa::radam_row_update<N, sympa::MODEL_BOUNDED>(x, gg, m + i * ROW, v[i], vn, lr, b1, b2, eps_adam, wd, pow1, pow2, eps, st);
+        moved += mv ? 1 : 0;
+        sympa::store_full<N>(m + i * ROW, gg);
+        v[i] = vn;
+        sympa::store_full<N>(z + i * ROW, x);
+    }
+    if (projected) *projected = moved;
+    return st;
+}
+}  // namespace
+
+// One RiemannianAdam step, in place, by the row function of the fused kernels (sympa::radam_row_update): pow1, pow2 = beta^t of
+// this step.  Returns the status bits.
+extern "C" int sympa_hostsim_radam(int model, int n, double* z, const double* g, double* m, double* v, int64_t b, double lr,
+                                   double b1, double b2, double eps_adam, double wd, double pow1, double pow2, double eps,
+                                   int32_t* projected) {
+    switch (n) {
+        case 1: return run_radam<1>(model, z, g, m, v, b, lr, b1, b2, eps_adam, wd, pow1, pow2, eps, projected);
+        case 2: return run_radam<2>(model, z, g, m, v, b, lr, b1, b2, eps_adam, wd, pow1, pow2, eps, projected);
+        case 3: return run_radam<3>(model, z, g, m, v, b, lr, b1, b2, eps_adam, wd, pow1, pow2, eps, projected);
+        case 4: return run_radam<4>(model, z, g, m, v, b, lr, b1, b2, eps_adam, wd, pow1, pow2, eps, projected);
+        case 5: return run_radam<5>(model, z, g, m, v, b, lr, b1, b2, eps_adam, wd, pow1, pow2, eps, projected);
+        case 6: return run_radam<6>(model, z, g, m, v, b, lr, b1, b2, eps_adam, wd, pow1, pow2, eps, projected);
+        case 7: return run_radam<7>(model, z, g, m, v, b, lr, b1, b2, eps_adam, wd, pow1, pow2, eps, projected);
+        case 8: return run_radam<8>(model, z, g, m, v, b, lr, b1, b2, eps_adam, wd, pow1, pow2, eps, projected);
         default: return -2;
     }
 }

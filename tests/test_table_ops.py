@@ -23,7 +23,7 @@ def test_hostsim_against_reference_goldens(n):
     out, moved = hostsim_table("projx", "upper", g["projx_in"])
     assert relmax(out, g["upper_projx"]) < 1e-12
     out, moved = hostsim_table("projx", "bounded", g["bounded_projx_in"])
-    assert relmax(out, g["bounded_projx"]) < 1e-9
+    assert relmax(out, g["bounded_projx"]) < 3e-13       # (measured: 9e-16 .. 2.7e-14 with the clamp as a matrix function of Z^H Z)
 
 
 def step_inputs(model, n, g):
@@ -66,7 +66,7 @@ def test_gpu_manifold_methods_against_goldens(dev, n):
     assert relmax(bd.egrad2rgrad(T(g["cayley_upper"]).to(dev), u).cpu(), g["bounded_egrad2rgrad"]) < 1e-13
     assert relmax(up.projx(T(g["projx_in"]).to(dev)).cpu(), g["upper_projx"]) < 1e-12
     assert up.projected_points == int((~torch.from_numpy(g["pcp_keep"])).numel()) or up.projected_points > 0
-    assert relmax(bd.projx(T(g["bounded_projx_in"]).to(dev)).cpu(), g["bounded_projx"]) < 1e-9
+    assert relmax(bd.projx(T(g["bounded_projx_in"]).to(dev)).cpu(), g["bounded_projx"]) < 1e-13     # (measured: 9e-16 .. 9.1e-15)
     # retr(x, u) = projx(x + u)   (siegel_manifold.py:74-87)
     x = T(g["upper_pts"]).to(dev)
     assert torch.equal(up.retr(x, 0.01 * u), up.projx(x + 0.01 * u))
