@@ -12,10 +12,13 @@ int launch_bwd_one_lane(const BwdArgs& a, int n, int model, bool scatter, hipStr
         case 4: return launch_bwd_n<4>(a, model, scatter, s);
         case 5: return launch_bwd_n<5>(a, model, scatter, s);
         case 6: return launch_bwd_n<6>(a, model, scatter, s);
-        case 7: return model == SYMPA_MODEL_UPPER ? launch_bwd_n7_upper(a, scatter, s) : launch_bwd_n7_bounded(a, scatter, s);
-        case 8: return model == SYMPA_MODEL_UPPER ? launch_bwd_n8_upper(a, scatter, s) : launch_bwd_n8_bounded(a, scatter, s);
         default: break;
     }
+    // n = 7, 8: the SYMPA_BWD_ONE_LANE instances (the dual lines never match here: that model left above)
+    const int m = model == SYMPA_MODEL_UPPER ? bwd_word::upper : bwd_word::bounded;
+#define SYMPA_BWD_ONE_LANE(M, N, F) \
+    if (n == N && m == bwd_word::M && scatter == bwd_word::F) return SYMPA_BWD_ONE_LANE_NAME(M, N, F)(a, s);
+#include "siegel_bwd_instances.hpp"
     return fail(SYMPA_ERR_UNSUPPORTED_DIMS, "one-pair-per-lane backward: dims 1..8");
 }
 }  // namespace sympa_hip

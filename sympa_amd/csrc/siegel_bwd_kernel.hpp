@@ -1,5 +1,5 @@
-// Backward kernel template shared by the translation units siegel_bwd.hip (n <= 6) and
-// siegel_bwd_n{7,8}_{upper,bounded}.hip.
+// Backward kernel template shared by the translation units siegel_bwd.hip, siegel_bwd_dual.hip (n <= 6) and the n = 7, 8
+// instances of siegel_bwd_one_lane_instance.hip (SYMPA_BWD_ONE_LANE lines of siegel_bwd_instances.hpp).
 #pragma once
 #include "siegel_common.hpp"
 #include "siegel_gather.hpp"
@@ -513,29 +513,30 @@ int launch_bwd_n(const BwdArgs& a, int model, bool scatter, hipStream_t s) {
                                       : launch_bwd_nm<N, sympa::MODEL_BOUNDED>(a, scatter, s);
 }
 
-// n = 7, 8: one translation unit per kernel -- siegel_bwd_n{7,8}_{upper,bounded}_{scatter,dense}.hip -- because the
-// fully unrolled adjoint of an 8 x 8 pair takes a minute or two to compile; the build compiles the units in parallel.
-#define SYMPA_BWD_LARGE(N, M) \
-    int launch_bwd_n##N##_##M##_scatter(const BwdArgs& a, hipStream_t s); \
-    int launch_bwd_n##N##_##M##_dense(const BwdArgs& a, hipStream_t s); \
-    inline int launch_bwd_n##N##_##M(const BwdArgs& a, bool scatter, hipStream_t s) { \
-        return scatter ? launch_bwd_n##N##_##M##_scatter(a, s) : launch_bwd_n##N##_##M##_dense(a, s); \
-    }
-SYMPA_BWD_LARGE(7, upper)
-SYMPA_BWD_LARGE(7, bounded)
-SYMPA_BWD_LARGE(8, upper)
-SYMPA_BWD_LARGE(8, bounded)
-SYMPA_BWD_LARGE(7, dual)
-SYMPA_BWD_LARGE(8, dual)
-#undef SYMPA_BWD_LARGE
+// The instances with a compile job of their own (siegel_bwd_instances.hpp: sixteen and eight lanes per pair, and n = 7, 8 of
+// these kernels because the fully unrolled adjoint of an 8 x 8 pair takes a minute or two to compile; the build compiles the
+// jobs in parallel).  Each list line has one wrapper function, named here, defined by the family's *_instance.hip compiled
+// with that line's words, declared below and called by the dispatch functions, which try the list's lines in turn.
+// The list's words as template arguments:
+namespace bwd_word {
+constexpr int upper = sympa::MODEL_UPPER, bounded = sympa::MODEL_BOUNDED, dual = sympa::MODEL_DUAL;
+constexpr bool dense = false, scatter = true;
+}  // namespace bwd_word
+#define SYMPA_BWD_COOP_NAME(M, N, F) launch_bwd_coop_##M##_##N##_##F
+#define SYMPA_BWD_HALF_NAME(M, N, F) launch_bwd_half_##M##_##N##_##F
+#define SYMPA_BWD_ONE_LANE_NAME(M, N, F) launch_bwd_n##N##_##M##_##F
+#define SYMPA_BWD_COOP(M, N, F) int SYMPA_BWD_COOP_NAME(M, N, F)(const BwdArgs& a, hipStream_t s);
+#define SYMPA_BWD_HALF(M, N, F) int SYMPA_BWD_HALF_NAME(M, N, F)(const BwdArgs& a, hipStream_t s);
+#define SYMPA_BWD_ONE_LANE(M, N, F) int SYMPA_BWD_ONE_LANE_NAME(M, N, F)(const BwdArgs& a, hipStream_t s);
+#include "siegel_bwd_instances.hpp"
 
-// dims 5..8 with eight lanes per pair (siegel_bwd_half*.hip; A/B and, where faster, the default)
+// dims 5..8 with eight lanes per pair (siegel_bwd_half.hip; A/B and, where faster, the default)
 int launch_bwd_half(const BwdArgs& a, int n, int model, bool scatter, hipStream_t s);
 
 // dims 9..16: siegel_bwd_rolled.hip (the same adjoint with rolled loops over scratch arrays)
 int launch_bwd_rolled(const BwdArgs& a, int n, int model, bool scatter, hipStream_t s);
 
-// compact dual: units of their own (siegel_bwd_dual.hip dims 1..6, siegel_bwd_n{7,8}_dual_{scatter,dense}.hip,
+// compact dual: units of their own (siegel_bwd_dual.hip dims 1..6, the dual lines of SYMPA_BWD_ONE_LANE dims 7, 8,
 // siegel_bwd_rolled_dual.hip dims 9..16), one pair per lane only
 int launch_bwd_dual(const BwdArgs& a, int n, bool scatter, hipStream_t s);
 int launch_bwd_rolled_dual(const BwdArgs& a, int n, bool scatter, hipStream_t s);

@@ -1,33 +1,9 @@
 // Split Siegel backward (dims 5..8, one pair per lane, two kernels through a caller-owned workspace): workspace size and dispatch.
-// Kernels: siegel_bwd_split_kernel.hpp, one per translation unit (siegel_bwd_split_spectral_*.hip, siegel_bwd_split_gradient_*.hip).
+// Kernels: siegel_bwd_split_kernel.hpp, one compile job each (the SYMPA_BWD_SPLIT_* instances of siegel_bwd_instances.hpp,
+// compiled from siegel_bwd_split_instance.hip).
 #include "siegel_bwd_split_kernel.hpp"
 
 namespace sympa_hip {
-int launch_bwd_split_spectral_upper_5(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_gradient_upper_5_scatter(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_gradient_upper_5_dense(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_spectral_upper_6(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_gradient_upper_6_scatter(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_gradient_upper_6_dense(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_spectral_upper_7(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_gradient_upper_7_scatter(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_gradient_upper_7_dense(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_spectral_upper_8(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_gradient_upper_8_scatter(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_gradient_upper_8_dense(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_spectral_bounded_5(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_gradient_bounded_5_scatter(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_gradient_bounded_5_dense(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_spectral_bounded_6(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_gradient_bounded_6_scatter(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_gradient_bounded_6_dense(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_spectral_bounded_7(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_gradient_bounded_7_scatter(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_gradient_bounded_7_dense(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_spectral_bounded_8(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_gradient_bounded_8_scatter(const SplitArgs& sa, hipStream_t s);
-int launch_bwd_split_gradient_bounded_8_dense(const SplitArgs& sa, hipStream_t s);
-
 namespace {
 int pack_len(int n, int model) {
     const int offd = n * (n - 1) / 2;
@@ -66,32 +42,18 @@ int launch_bwd_split(const BwdArgs& a, int n, int model, bool scatter, void* wor
     sa.a.f.flags &= ~SYMPA_INTERNAL_FLAG_STAGGER;
     if (a.f.idx1 != nullptr && a.f.b >= 2048 * 64 && a.f.num_rows * (int64_t)(16 * n * n) >= ((int64_t)12 << 20))
         sa.a.f.flags |= SYMPA_INTERNAL_FLAG_STAGGER;
-    const bool upper = model == SYMPA_MODEL_UPPER;
-    int rc;
-    switch (n) {
-        case 5: rc = upper ? launch_bwd_split_spectral_upper_5(sa, s) : launch_bwd_split_spectral_bounded_5(sa, s); break;
-        case 6: rc = upper ? launch_bwd_split_spectral_upper_6(sa, s) : launch_bwd_split_spectral_bounded_6(sa, s); break;
-        case 7: rc = upper ? launch_bwd_split_spectral_upper_7(sa, s) : launch_bwd_split_spectral_bounded_7(sa, s); break;
-        case 8: rc = upper ? launch_bwd_split_spectral_upper_8(sa, s) : launch_bwd_split_spectral_bounded_8(sa, s); break;
-        default: return fail(SYMPA_ERR_UNSUPPORTED_DIMS, "split backward: dims 5..8");
-    }
+    const int m = model == SYMPA_MODEL_UPPER ? bwd_word::upper : bwd_word::bounded;
+    int rc;                 // stage 1: the list's lines as one if / else if chain that ends in the refusal
+#define SYMPA_BWD_SPLIT_SPECTRAL(M, N) \
+    if (n == N && m == bwd_word::M) rc = SYMPA_BWD_SPLIT_SPECTRAL_NAME(M, N)(sa, s); else
+#include "siegel_bwd_instances.hpp"
+        return fail(SYMPA_ERR_UNSUPPORTED_DIMS, "split backward: dims 5..8");
     if (rc != 0) return rc;
     const auto gradient = [&]() -> int {
-    switch (n) {
-        case 5:
-            if (upper) return scatter ? launch_bwd_split_gradient_upper_5_scatter(sa, s) : launch_bwd_split_gradient_upper_5_dense(sa, s);
-            return scatter ? launch_bwd_split_gradient_bounded_5_scatter(sa, s) : launch_bwd_split_gradient_bounded_5_dense(sa, s);
-        case 6:
-            if (upper) return scatter ? launch_bwd_split_gradient_upper_6_scatter(sa, s) : launch_bwd_split_gradient_upper_6_dense(sa, s);
-            return scatter ? launch_bwd_split_gradient_bounded_6_scatter(sa, s) : launch_bwd_split_gradient_bounded_6_dense(sa, s);
-        case 7:
-            if (upper) return scatter ? launch_bwd_split_gradient_upper_7_scatter(sa, s) : launch_bwd_split_gradient_upper_7_dense(sa, s);
-            return scatter ? launch_bwd_split_gradient_bounded_7_scatter(sa, s) : launch_bwd_split_gradient_bounded_7_dense(sa, s);
-        case 8:
-            if (upper) return scatter ? launch_bwd_split_gradient_upper_8_scatter(sa, s) : launch_bwd_split_gradient_upper_8_dense(sa, s);
-            return scatter ? launch_bwd_split_gradient_bounded_8_scatter(sa, s) : launch_bwd_split_gradient_bounded_8_dense(sa, s);
-        default: return fail(SYMPA_ERR_UNSUPPORTED_DIMS, "split backward: dims 5..8");
-    }
+#define SYMPA_BWD_SPLIT_GRADIENT(M, N, F) \
+        if (n == N && m == bwd_word::M && scatter == bwd_word::F) return SYMPA_BWD_SPLIT_GRADIENT_NAME(M, N, F)(sa, s);
+#include "siegel_bwd_instances.hpp"
+        return fail(SYMPA_ERR_UNSUPPORTED_DIMS, "split backward: dims 5..8");
     };
     rc = gradient();
     if (rc != 0) return rc;

@@ -423,7 +423,14 @@ int launch_bwd_split_gradient(const SplitArgs& sa, hipStream_t s) {
     return 0;
 }
 
-// siegel_bwd_split.hip: workspace size and dispatch (one translation unit per kernel: siegel_bwd_split_*_*.hip)
+// One compile job per kernel: siegel_bwd_split_instance.hip, once per SYMPA_BWD_SPLIT_* line of siegel_bwd_instances.hpp
+#define SYMPA_BWD_SPLIT_SPECTRAL_NAME(M, N) launch_bwd_split_spectral_##M##_##N
+#define SYMPA_BWD_SPLIT_GRADIENT_NAME(M, N, F) launch_bwd_split_gradient_##M##_##N##_##F
+#define SYMPA_BWD_SPLIT_SPECTRAL(M, N) int SYMPA_BWD_SPLIT_SPECTRAL_NAME(M, N)(const SplitArgs& sa, hipStream_t s);
+#define SYMPA_BWD_SPLIT_GRADIENT(M, N, F) int SYMPA_BWD_SPLIT_GRADIENT_NAME(M, N, F)(const SplitArgs& sa, hipStream_t s);
+#include "siegel_bwd_instances.hpp"
+
+// siegel_bwd_split.hip: workspace size and dispatch
 int64_t bwd_split_workspace_bytes(int64_t b, int n, int model);
 bool bwd_split_available(int n, int model);
 int launch_bwd_split(const BwdArgs& a, int n, int model, bool scatter, void* workspace, int64_t workspace_bytes, hipStream_t s);

@@ -1,5 +1,6 @@
 // Kernel of the sixteen-lanes-per-pair Siegel backward (routines: siegel_coop_bwd.hpp), both models, instantiated per
-// model, matrix size M = n and output form by siegel_bwd_coop_*.hip.  Same argument block, outputs and fused AverageDistortionLoss as the
+// model, matrix size M = n and output form by siegel_bwd_coop_instance.hip (eight lanes per pair: siegel_bwd_half_instance.hip),
+// once per line of siegel_bwd_instances.hpp.  Same argument block, outputs and fused AverageDistortionLoss as the
 // one-pair-per-lane kernel (siegel_bwd_kernel.hpp); SCATTER: atomic adds of the gradient rows into the table gradient,
 // otherwise per-pair rows [b, 2, n, n].
 #pragma once
@@ -336,39 +337,7 @@ int launch_coop_bwd_ms(const BwdArgs& a, hipStream_t s) {
     return 0;
 }
 
-// n = 9..16, both models (siegel_bwd_coop_<model>_<n>_{dense,scatter}.hip: one kernel per translation unit; siegel_bwd_coop.hip)
+// n = 9..16, both models: siegel_bwd_coop.hip, over the SYMPA_BWD_COOP instances (declared by siegel_bwd_kernel.hpp)
 int launch_bwd_coop(const BwdArgs& a, int n, int model, bool scatter, hipStream_t s);
-int launch_bwd_coop_upper_9_dense(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_upper_9_scatter(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_upper_10_dense(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_upper_10_scatter(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_upper_11_dense(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_upper_11_scatter(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_upper_12_dense(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_upper_12_scatter(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_upper_13_dense(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_upper_13_scatter(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_upper_14_dense(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_upper_14_scatter(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_upper_15_dense(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_upper_15_scatter(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_upper_16_dense(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_upper_16_scatter(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_bounded_9_dense(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_bounded_9_scatter(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_bounded_10_dense(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_bounded_10_scatter(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_bounded_11_dense(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_bounded_11_scatter(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_bounded_12_dense(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_bounded_12_scatter(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_bounded_13_dense(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_bounded_13_scatter(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_bounded_14_dense(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_bounded_14_scatter(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_bounded_15_dense(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_bounded_15_scatter(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_bounded_16_dense(const BwdArgs& a, hipStream_t s);
-int launch_bwd_coop_bounded_16_scatter(const BwdArgs& a, hipStream_t s);
 
 }  // namespace sympa_hip

@@ -146,11 +146,15 @@ def test_integration_md_stub_compiles_and_matches_the_binding():
 
 
 def test_every_translation_unit_passed_the_dpp_hazard_scan():
-    """__graft_entry__.build() scans the gfx950 assembly of every .hip unit for the DPP hazards the compiler cannot see in
-    inline asm (tools/check_dpp_hazards.py) and rebuilds a unit that fails with the wait states inside the asm statements;
-    its report must list every unit as clean in the end."""
+    """__graft_entry__.build() scans the gfx950 assembly of every unit it compiles (__graft_entry__.hip_units(): the plain .hip
+    files and one unit per line of csrc/siegel_bwd_instances.hpp) for the DPP hazards the compiler cannot see in inline asm
+    (tools/check_dpp_hazards.py) and rebuilds a unit that fails with the wait states inside the asm statements; its report must
+    list every unit as clean in the end.  No .hip file of csrc/ may stay outside the units."""
     import os
+    import __graft_entry__ as entry
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "sympa_amd", "csrc")
+    units = entry.hip_units()
+    assert {src for _, src, _ in units} == {f for f in os.listdir(csrc) if f.endswith(".hip")}
     report = os.path.join(csrc, "dpp_hazard_report.txt")
     if not os.path.exists(os.path.join(csrc, "libsympa_hip.so")):
         import pytest
@@ -159,8 +163,7 @@ def test_every_translation_unit_passed_the_dpp_hazard_scan():
     # `make -C sympa_amd/csrc` forwards to): it may contain the hazardous units -- a failure, not a skip
     assert os.path.exists(report), "libsympa_hip.so exists but dpp_hazard_report.txt does not: built outside __graft_entry__.build()"
     lines = {l.split()[0]: l.strip() for l in open(report) if l.strip() and not l.startswith("#")}
-    units = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
-    assert sorted(lines) == units
+    assert sorted(lines) == [name for name, _, _ in units]
     dpp = {u: l.split(";")[0].strip() for u, l in lines.items()}
     assert all(l.endswith("clean") for l in dpp.values()), [l for l in dpp.values() if not l.endswith("clean")]
     # ... and (round 5, tools/dma_reload_check.py) no LDS-DMA instruction of any unit sits behind a scratch reload: such a reload
@@ -170,3 +173,26 @@ def test_every_translation_unit_passed_the_dpp_hazard_scan():
         m = re.search(r"(\d+) LDS-DMA instructions, (\d+) behind a scratch reload", l)
         assert m, f"{u}: no LDS-DMA scan in the report (rebuild with __graft_entry__.build())"
         assert int(m.group(2)) == 0, l
+
+
+def test_the_instance_list_is_the_cross_product_of_every_family():
+    """csrc/siegel_bwd_instances.hpp, read the way the build reads it, against the families restated here: every backward kernel
+    with a compile job of its own, once, and no unit name taken twice.  (The list also makes the declarations and the dispatch:
+    a wrapper the dispatch names and no unit defines fails when build() loads the library, which binds every symbol.)"""
+    import __graft_entry__ as entry
+    forms = ("dense", "scatter")
+    want = [("COOP", m, n, f) for m in ("upper", "bounded") for n in range(9, 17) for f in forms]
+    want += [("HALF", m, n, f) for m in ("upper", "bounded") for n in range(5, 9) for f in forms]
+    want += [("SPLIT_SPECTRAL", m, n, None) for m in ("upper", "bounded") for n in range(5, 9)]
+    want += [("SPLIT_GRADIENT", m, n, f) for m in ("upper", "bounded") for n in range(5, 9) for f in forms]
+    want += [("ONE_LANE", m, n, f) for m in ("upper", "bounded", "dual") for n in (7, 8) for f in forms]
+    got = entry.bwd_instances()
+    assert len(got) == len(set(got)) == 84
+    assert set(got) == set(want)
+    units = entry.hip_units()
+    names = [name[:-4] if name.endswith(".hip") else name for name, _, _ in units]
+    assert len(set(names)) == len(names)                    # one object file per unit
+    instances = [u for u in units if u[2]]
+    assert len(instances) == 84 and len({tuple(d) + (src,) for _, src, d in instances}) == 84
+    assert {"siegel_bwd_coop_upper_9_dense", "siegel_bwd_half_bounded_8_scatter", "siegel_bwd_split_spectral_upper_5",
+            "siegel_bwd_split_gradient_bounded_6_dense", "siegel_bwd_n7_dual_scatter"} <= {name for name, _, _ in instances}
