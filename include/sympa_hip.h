@@ -572,6 +572,42 @@ int sympa_graph_hop_rows(const int64_t* rowptr, const int32_t* cols, int64_t num
 int sympa_graph_distortion_rows(const double* dist, int64_t ld_dist, const int32_t* hops, int64_t ld_hops, int64_t row_begin,
                                 int64_t row_count, int64_t num_nodes, double* row_sum, int64_t* row_pairs, void* stream);
 
+/* Weighted shortest-path distances from the sources src_begin .. src_begin + src_count - 1 to every node of a graph with
+ * non-negative edge weights: what the reference's preprocessing computes for all pairs of a weighted graph
+ * (preprocess.py:108-114), a block of rows at a time (csrc/graph_sssp.hip: pull-based multi-source Bellman-Ford, one workgroup
+ * per group of 8 consecutive sources, sweeps separated by workgroup barriers only).
+ *   rowptr      [num_nodes + 1] int64, cols [num_entries] int32, weights [num_entries] fp64: the adjacency as a SYMMETRIC CSR
+ *               (both directions of every edge present, with the same weight), self-loops and duplicate edges removed.  A
+ *               weight of 0 is legal and -0.0 is taken as 0.
+ *   out         [src_count, row_stride] fp64, row_stride >= num_nodes: out[s - src_begin][v] = the minimum over the paths from
+ *               s to v of the left-to-right fp64 sum of their weights, starting at s: bit for bit what Dijkstra from s
+ *               computes.  0 on the diagonal, +inf where v cannot be reached.  Every element [r][v < num_nodes] is written
+ *               exactly once; nothing is pre-filled and the padding beyond num_nodes is untouched.  out[i][j] and out[j][i]
+ *               may differ in their last bits (each row is summed from its own source); nothing symmetrises them.
+ *   workspace   sympa_graph_weighted_workspace_bytes(num_nodes, src_count) = ceil(src_count / 8) * 8 * (num_nodes + 1) * 8
+ *               bytes of caller-owned, 8-byte aligned device memory: one fp64 [num_nodes][8] plane per group of sources, then
+ *               one int64 per source, which on return holds the number of sweeps the group of that source ran (timing
+ *               tools read it).  0 for num_nodes <= 0 or src_count <= 0.
+ * The values do not depend on how the sources are split into calls: the result is the unique least fixed point of the
+ * relaxation.
+ * A column outside [0, num_nodes) or a rowptr entry outside [0, num_entries] is skipped and sets SYMPA_ST_BAD_INDEX in
+ * `status`; a weight that is NaN, negative or infinite is skipped and sets SYMPA_ST_NONFINITE; word 1 counts the entries of
+ * both kinds.  Arguments are validated before any launch; src_count == 0 is a no-op. */
+int64_t sympa_graph_weighted_workspace_bytes(int64_t num_nodes, int64_t src_count);
+int sympa_graph_weighted_rows(const int64_t* rowptr, const int32_t* cols, const double* weights, int64_t num_nodes,
+                              int64_t num_entries, int64_t src_begin, int64_t src_count, double* out, int64_t row_stride,
+                              void* workspace, int64_t workspace_bytes, int32_t* status, void* stream);
+
+/* Distortion of a block of manifold distance rows against the weighted graph distance rows of the same nodes (metrics.py:21
+ * over the pairs i < j): the fp64 twin of sympa_graph_distortion_rows.
+ *   row_sum[r]   = sum over j > i, 0 < gdist[r][j] < inf of |dist[r][j] - gdist[r][j]| / gdist[r][j],   i = row_begin + r
+ *   row_pairs[r] = the number of those j
+ * dist [row_count, ld_dist] and gdist [row_count, ld_g] (sympa_graph_weighted_rows) fp64, both leading dimensions >= num_nodes.
+ * Each row is summed in an order that depends on the row alone, so a row's value is bitwise the same in every blocking. */
+int sympa_graph_weighted_distortion_rows(const double* dist, int64_t ld_dist, const double* gdist, int64_t ld_g,
+                                         int64_t row_begin, int64_t row_count, int64_t num_nodes, double* row_sum,
+                                         int64_t* row_pairs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,6 +70,9 @@ SYMBOLS = (
     "sympa_graph_hops_workspace_bytes",
     "sympa_graph_hop_rows",
     "sympa_graph_distortion_rows",
+    "sympa_graph_weighted_workspace_bytes",
+    "sympa_graph_weighted_rows",
+    "sympa_graph_weighted_distortion_rows",
 )
 
 _c_double_p = ctypes.c_void_p
@@ -320,6 +323,14 @@ def load():
     lib.sympa_graph_distortion_rows.restype = C.c_int
     lib.sympa_graph_distortion_rows.argtypes = [_c_double_p, C.c_int64, _c_i32_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                                 _c_double_p, _c_i64_p, C.c_void_p]
+    lib.sympa_graph_weighted_workspace_bytes.restype = C.c_int64
+    lib.sympa_graph_weighted_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+    lib.sympa_graph_weighted_rows.restype = C.c_int
+    lib.sympa_graph_weighted_rows.argtypes = [_c_i64_p, _c_i32_p, _c_double_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                              _c_double_p, C.c_int64, C.c_void_p, C.c_int64, _c_i32_p, C.c_void_p]
+    lib.sympa_graph_weighted_distortion_rows.restype = C.c_int
+    lib.sympa_graph_weighted_distortion_rows.argtypes = [_c_double_p, C.c_int64, _c_double_p, C.c_int64, C.c_int64, C.c_int64,
+                                                         C.c_int64, _c_double_p, _c_i64_p, C.c_void_p]
     _lib = lib
     return lib
 

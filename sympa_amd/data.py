@@ -8,6 +8,8 @@
     lexicographic order with BFS distances (what preprocess.py:101-126 produces through networkit);
   * DistributedSampler semantics for sharding a triplet list over ranks (train.py:105-110).
 """
+import os
+
 import numpy as np
 import torch
 
@@ -95,6 +97,7 @@ def sample_pairs(num_points, batch, batch_id=0, seed=42):
 def graph_triplets(graph):
     """All (i, j, d) with i < j, 0 < d < inf of a networkx graph whose nodes are relabelled by
     sorted() (preprocess.py:152-153,101-126); lexicographic order; BFS hop distances (exact ints).
+    Edge weights are IGNORED: a weighted graph gets its hop counts here (weighted_graph_triplets honours them).
     Returns (int64 [T,3] tensor, id2node dict)."""
     import networkx as nx
     from scipy.sparse.csgraph import shortest_path
@@ -111,6 +114,35 @@ def graph_triplets(graph):
     keep = np.isfinite(d) & (d > 0)
     trip = np.stack((iu[keep], ju[keep], d[keep].astype(np.int64)), 1).astype(np.int64)
     return torch.from_numpy(trip), id2node
+
+
+def load_edges(path, name=None):
+    """The reference's .edges reader (preprocess.py:76-86) as an nx.Graph: one edge per line, fields split on whitespace; a third
+    field that is a plain decimal number (`replace(".", "", 1).isdigit()`: digits with at most one point, no sign, no exponent)
+    is the edge's float weight, any other line gives an unweighted edge.  A repeated edge keeps its last line."""
+    import networkx as nx
+    graph = nx.Graph(name=os.path.splitext(os.path.basename(str(path)))[0] if name is None else name)
+    with open(path, "r") as f:
+        for line in f:
+            line = line.strip().split()
+            if len(line) < 2:
+                continue
+            if len(line) == 2 or not line[2].replace(".", "", 1).isdigit():
+                graph.add_edge(line[0], line[1])
+            else:
+                graph.add_edge(line[0], line[1], weight=float(line[2]))
+    return graph
+
+
+def weighted_graph_triplets(graph):
+    """All (i, j) with i < j and 0 < d < inf of a WEIGHTED networkx graph (every edge carries a weight) with their weighted
+    shortest-path distances (preprocess.py:108-126), nodes relabelled by sorted(), lexicographic order, each distance the fp64
+    sum along the lightest path from i.  Returns (ids int64 [T, 2], dist fp64 [T], id2node): the form load_preprocessed returns.
+    Computed on the CPU through sympa_amd.graph.WeightedGraphDistances, a block of rows at a time."""
+    from sympa_amd.graph import WeightedGraphDistances, weighted_graph_csr
+    rowptr, cols, weights, id2node = weighted_graph_csr(graph)
+    ids, dist = WeightedGraphDistances(rowptr, cols, weights).triplets()
+    return ids, dist, id2node
 
 
 def named_graph(name):

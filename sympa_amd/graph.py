@@ -9,6 +9,12 @@ against itself and be scored over all of its pairs without the matrix ever exist
   graph_csr(graph)             networkx graph -> (rowptr, cols, id2node), relabelled and cleaned exactly like graph_triplets
   host_hop_rows(...)           the numpy restatement of the kernel's algorithm (CPU tests, CPU tensors)
   GraphDistances(rowptr, cols) rows / pairs / triplets / neighbor_csr on the CSR's device
+
+Weighted graphs (preprocess.py:76-86,108-114: a third column of an .edges file, float distances) have the same three pieces over
+fp64 rows: weighted_graph_csr, host_weighted_rows and WeightedGraphDistances (csrc/graph_sssp.hip through
+ops.graph_weighted_rows).  A row is the left-to-right fp64 sum of the lightest path FROM ITS OWN SOURCE, bit for bit what Dijkstra
+from that source computes; rows i and j may therefore disagree about the pair (i, j) in the last bits, and nothing here
+symmetrises them (the reference keeps shortest_paths[i][j] with i < j, taken from row i).
 """
 import numpy as np
 import torch
@@ -28,7 +34,8 @@ def graph_csr(graph):
     g = nx.Graph(nx.convert_node_labels_to_integers(graph, ordering="sorted"))
     if any("weight" in d for _, _, d in g.edges(data=True)):
         raise NotImplementedError("graph_csr computes hop distances of unweighted graphs only; "
-                                  "use data.graph_triplets for a weighted graph")
+                                  "use data.graph_triplets for a weighted graph (it ignores the weights), or "
+                                  "weighted_graph_csr / WeightedGraphDistances for its weighted distances")
     N = len(nodes)
     e = np.array([(u, v) for u, v in g.edges() if u != v], dtype=np.int64).reshape(-1, 2)
     key = np.unique(np.concatenate((e[:, 0] * N + e[:, 1], e[:, 1] * N + e[:, 0])))
@@ -217,6 +224,220 @@ class GraphDistances:
         cols = self.cols.to(torch.int64)
         keep = (cols >= 0) & (cols < N) & (cols != rows)
         key = torch.unique(rows[keep] * N + cols[keep])
+        r = key // N
+        rowptr = torch.zeros(N + 1, dtype=torch.int64, device=self.device)
+        rowptr[1:] = torch.cumsum(torch.bincount(r, minlength=N), 0)
+        return rowptr, (key - r * N).to(torch.int32)
+
+
+# ---------------------------------------------------------------------------------------------------
+# Weighted graphs
+# ---------------------------------------------------------------------------------------------------
+def weighted_graph_csr(graph):
+    """(rowptr int64 [N + 1], cols int32 [E], weights fp64 [E], id2node) of a weighted networkx graph as CPU tensors, cleaned like
+    graph_csr: nodes relabelled by sorted(), parallel edges collapsed (nx.Graph: a repeated edge keeps its last weight, as in the
+    reference's loader), self-loops dropped, both directions of every edge stored with the same weight, each row's columns
+    ascending.  Every edge must carry a weight (nx.is_weighted, the reference's own switch at preprocess.py:108); a weight of 0
+    is legal, a NaN, negative or infinite one is refused."""
+    import networkx as nx
+
+    nodes = sorted(graph.nodes())
+    id2node = {i: node for i, node in enumerate(nodes)}
+    g = nx.Graph(nx.convert_node_labels_to_integers(graph, ordering="sorted"))
+    if not nx.is_weighted(g):
+        raise ValueError("weighted_graph_csr needs a weight on every edge (networkx.is_weighted); use graph_csr for the hop "
+                         "distances of an unweighted graph")
+    N = len(nodes)
+    edges = [(u, v, float(d["weight"])) for u, v, d in g.edges(data=True) if u != v]
+    e = np.array([(u, v) for u, v, _ in edges], dtype=np.int64).reshape(-1, 2)
+    w = np.array([x for _, _, x in edges], dtype=np.float64)
+    bad = ~((w >= 0) & (w < np.inf))
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"edge ({id2node[int(e[k, 0])]!r}, {id2node[int(e[k, 1])]!r}) has weight {w[k]!r}: weights must be finite "
+                         "and not negative")
+    key = np.concatenate((e[:, 0] * N + e[:, 1], e[:, 1] * N + e[:, 0]))
+    order = np.argsort(key, kind="stable")                                # nx.Graph: every key is there once
+    key = key[order]
+    rows = key // max(N, 1)
+    rowptr = np.zeros(N + 1, dtype=np.int64)
+    rowptr[1:] = np.cumsum(np.bincount(rows, minlength=N))
+    cols = (key - rows * N).astype(np.int32)
+    weights = np.abs(np.concatenate((w, w))[order])                       # -0.0 -> 0.0
+    return torch.from_numpy(rowptr), torch.from_numpy(cols), torch.from_numpy(weights), id2node
+
+
+def _as_numpy(x, dtype):
+    return np.asarray(x.cpu() if torch.is_tensor(x) else x).astype(dtype)
+
+
+def host_weighted_rows(rowptr, cols, weights, begin, count):
+    """fp64 [count, N] ndarray of weighted shortest-path distances from the sources [begin, begin + count): 0 on the diagonal,
+    +inf for unreachable nodes, each row the left-to-right fp64 sum of its lightest path from its own source.  The fixed point
+    csrc/graph_sssp.hip computes, reached here by Jacobi sweeps in numpy: every sweep pulls min over the neighbours u of
+    d[u] + w(u, v) per node (np.minimum.reduceat) for a chunk of sources at once, until a sweep changes nothing.  The order of
+    the relaxations cannot change a bit of the result, so this equals the kernel's in-place sweeps and Dijkstra.  Entries with a
+    column outside [0, N) or a NaN, negative or infinite weight are skipped and row ranges are clamped, as the kernel does."""
+    rowptr, cols = _as_numpy(rowptr, np.int64), _as_numpy(cols, np.int64)
+    weights = _as_numpy(weights, np.float64)
+    N, E = rowptr.size - 1, cols.size
+    begin, count = int(begin), int(count)
+    if N <= 0 or begin < 0 or count < 0 or begin + count > N:
+        raise ValueError(f"source block [{begin}, {begin + count}) outside [0, {N})")
+    if weights.size != E:
+        raise ValueError(f"{E} columns but {weights.size} weights")
+    beg, end = np.clip(rowptr[:-1], 0, E), np.clip(rowptr[1:], 0, E)
+    deg = np.maximum(end - beg, 0)
+    first = np.cumsum(deg) - deg
+    entry = np.arange(int(deg.sum())) - np.repeat(first, deg) + np.repeat(beg, deg)
+    owner = np.repeat(np.arange(N), deg)
+    with np.errstate(invalid="ignore"):
+        ok = (cols[entry] >= 0) & (cols[entry] < N) & (weights[entry] >= 0) & (weights[entry] < np.inf)
+    owner, nbr, w = owner[ok], cols[entry][ok], weights[entry][ok]
+    out = np.full((count, N), np.inf, dtype=np.float64)
+    out[np.arange(count), begin + np.arange(count)] = 0.0
+    if owner.size == 0:
+        return out
+    starts = np.flatnonzero(np.r_[True, owner[1:] != owner[:-1]])
+    pulled = owner[starts]
+    for c0 in range(0, count, 64):
+        d = np.ascontiguousarray(out[c0:c0 + 64].T)                       # [N, sources of the chunk]
+        for _ in range(N):
+            new = d.copy()
+            new[pulled] = np.minimum(d[pulled], np.minimum.reduceat(d[nbr] + w[:, None], starts, axis=0))
+            if np.array_equal(new, d):
+                break
+            d = new
+        out[c0:c0 + 64] = d.T
+    return out
+
+
+class WeightedGraphDistances(GraphDistances):
+    """Weighted shortest-path distances of one graph, computed on demand a block of source rows at a time: GraphDistances over
+    fp64 rows.
+
+    rowptr / cols / weights: the symmetric CSR of weighted_graph_csr (tensors or ndarrays); `device`: where the CSR and every
+    result live (default: the CSR's own device).  On a GPU the rows come from the HIP kernel behind ops.graph_weighted_rows, on the
+    CPU from host_weighted_rows.  No call holds more than one block of rows: at most max_block_bytes of fp64 [R, N] (R a multiple
+    of 64, at least 64) plus the kernel's workspace of 8 (N + 1) bytes per row."""
+
+    def __init__(self, rowptr, cols, weights, device=None, max_block_bytes=128 << 20):
+        super().__init__(rowptr, cols, device=device, max_block_bytes=max_block_bytes)
+        self.weights = torch.as_tensor(weights).to(device=self.device, dtype=torch.float64).contiguous()
+        if self.weights.shape != self.cols.shape:
+            raise ValueError(f"{self.cols.numel()} columns but {self.weights.numel()} weights")
+
+    def rows_per_block(self, max_block_bytes):
+        """Source rows per block for a byte budget (8 N bytes per row): whole groups of 64 rows, at least one, at most the
+        graph."""
+        R = max(64, (int(max_block_bytes) // (8 * self.num_nodes)) // 64 * 64)
+        return min(R, -(-self.num_nodes // 64) * 64)
+
+    def workspace_bytes(self, count=None):
+        """Bytes of kernel workspace behind a block of `count` rows (default: a full block): 8 (N + 1) per row, rows in eights."""
+        count = self.block_rows if count is None else int(count)
+        return -(-count // 8) * 8 * (self.num_nodes + 1) * 8 if count > 0 else 0
+
+    def rows(self, begin, count, out=None):
+        """fp64 [count, N]: distances from the sources [begin, begin + count); 0 on the diagonal, +inf for unreachable nodes.
+        `out` (fp64 [>= count, N] on the device) is written and its first `count` rows returned."""
+        begin, count = int(begin), int(count)
+        N = self.num_nodes
+        if begin < 0 or count < 0 or begin + count > N:
+            raise ValueError(f"source block [{begin}, {begin + count}) outside [0, {N})")
+        if self.device.type != "cuda":
+            got = torch.from_numpy(host_weighted_rows(self.rowptr, self.cols, self.weights, begin, count))
+            if out is None:
+                return got
+            out[:count].copy_(got)
+            return out[:count]
+        from sympa_amd import ops
+        need = self.workspace_bytes(count)
+        if self._ws is None or self._ws.numel() * 8 < need:
+            self._ws = None
+            self._ws = torch.empty(max(need, self.workspace_bytes(min(self.block_rows, N))) // 8, dtype=torch.int64,
+                                   device=self.device)
+        return ops.graph_weighted_rows(self.rowptr, self.cols, self.weights, begin, count, out=out, workspace=self._ws)
+
+    def _block_buffer(self):
+        if self._buf is None:
+            self._buf = torch.empty(min(self.block_rows, self.num_nodes), self.num_nodes, dtype=torch.float64, device=self.device)
+        return self._buf
+
+    def pairs(self, src_dst_ids):
+        """fp64 [b] distances of the pairs src_dst_ids[:, :2] (any order, any device), each taken from the row of its FIRST node,
+        `inf` for unreachable pairs.  The pairs are grouped by the block of their source; every block that is needed is computed
+        once and gathered from."""
+        ids = torch.as_tensor(src_dst_ids)
+        if ids.dim() != 2 or ids.shape[1] < 2:
+            raise ValueError(f"src_dst_ids must be [b, >=2], got {tuple(ids.shape)}")
+        ids = ids[:, :2].to(device=self.device, dtype=torch.int64)
+        N = self.num_nodes
+        out = torch.empty(ids.shape[0], dtype=torch.float64, device=self.device)
+        if ids.shape[0] == 0:
+            return out
+        if int(ids.min()) < 0 or int(ids.max()) >= N:
+            raise IndexError(f"a node id is outside [0, {N})")
+        buf = self._block_buffer()
+        R = buf.shape[0]
+        order = torch.argsort(ids[:, 0], stable=True)
+        src, dst = ids[order, 0], ids[order, 1]
+        needed, counts = torch.unique_consecutive(src // R, return_counts=True)
+        start = 0
+        for k, end in zip(needed.tolist(), torch.cumsum(counts, 0).tolist()):
+            b = k * R
+            rows = self.rows(b, min(R, N - b), out=buf)
+            out[order[start:end]] = rows[src[start:end] - b, dst[start:end]]
+            start = end
+        return out
+
+    def _listed(self, b, rows, col):
+        """The pairs of a block a triplet list holds: j > i with 0 < D[i][j] < inf."""
+        i = torch.arange(b, b + rows.shape[0], device=self.device)
+        return (rows > 0) & torch.isfinite(rows) & (col[None, :] > i[:, None])
+
+    def count_triplets(self):
+        """Number of pairs i < j with 0 < D[i][j] < inf (one pass over every row block)."""
+        total = torch.zeros((), dtype=torch.int64, device=self.device)
+        col = torch.arange(self.num_nodes, device=self.device)
+        for b, rows in self.blocks():
+            total += self._listed(b, rows, col).sum()
+        return int(total)
+
+    def triplets(self, max_bytes=TRIPLETS_MAX_BYTES):
+        """(ids int64 [T, 2], dist fp64 [T]) on the device, the form data.load_preprocessed returns: every i < j with
+        0 < D[i][j] < inf in lexicographic order, the distance taken from row i, built block by block.  Raises MemoryError when
+        the upper bound N (N - 1) / 2 on T exceeds max_bytes / 24 and the counted T does too."""
+        N = self.num_nodes
+        if N * (N - 1) // 2 * 24 > max_bytes:
+            T = self.count_triplets()
+            if T * 24 > max_bytes:
+                raise MemoryError(f"{T} triplets need {T * 24} bytes, above the budget of {int(max_bytes)} bytes: stream the rows "
+                                  "(WeightedGraphDistances.rows / pairs, Model.evaluate_all_pairs) instead of materialising them")
+        col = torch.arange(N, device=self.device)
+        ids, dist = [], []
+        for b, rows in self.blocks():
+            r, j = torch.nonzero(self._listed(b, rows, col), as_tuple=True)                     # row-major: lexicographic
+            ids.append(torch.stack((r + b, j), 1))
+            dist.append(rows[r, j])
+        if not ids:
+            return torch.zeros(0, 2, dtype=torch.int64, device=self.device), torch.zeros(0, dtype=torch.float64, device=self.device)
+        return torch.cat(ids), torch.cat(dist)
+
+    def neighbor_csr(self):
+        """(rowptr int64 [N + 1], cols int32 [E]) of the neighbour sets the reference's mAP uses (sympa/metrics.py:31-36), rows
+        ascending and unique: what ops.map_rows and MeanAveragePrecisionMetric.from_csr take.  On a weighted graph a neighbour is
+        a node at DISTANCE EXACTLY 1.0, not an adjacent node: j is in the set of i when D[i][j] == 1.0 or D[j][i] == 1.0 (either
+        row, as a union).  Built in one pass over the row blocks."""
+        N = self.num_nodes
+        keys = []
+        for b, rows in self.blocks():
+            r, j = torch.nonzero(rows == 1.0, as_tuple=True)
+            i = r + b
+            keep = i != j
+            i, j = i[keep], j[keep]
+            keys.append(torch.cat((i * N + j, j * N + i)))
+        key = torch.unique(torch.cat(keys)) if keys else torch.zeros(0, dtype=torch.int64, device=self.device)
         r = key // N
         rowptr = torch.zeros(N + 1, dtype=torch.int64, device=self.device)
         rowptr[1:] = torch.cumsum(torch.bincount(r, minlength=N), 0)

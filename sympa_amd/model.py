@@ -391,10 +391,14 @@ class Model(nn.Module):
         behind distance_matrix(row_begin, row_count)) and of GraphDistances.rows stream through one reused pair of [R, N] buffers,
         fp64 and int32, R from max_block_bytes over both (12 N bytes per row, whole words of 64 rows); each block is reduced on the
         device to per-row sums and pair counts (ops.graph_distortion_rows: a row's sum depends on the row alone), so the value does
-        not depend on the block size.  With `group` set or a default process group initialised every rank takes its contiguous
+        not depend on the block size.  A sympa_amd.graph.WeightedGraphDistances is taken as well: its rows are fp64 (16 N bytes per
+        row over both buffers) and ops.graph_weighted_distortion_rows reduces them, over the pairs with 0 < d_graph < inf, each
+        graph distance taken from the row of the smaller node.
+        With `group` set or a default process group initialised every rank takes its contiguous
         share of the rows and the zero-padded [N] vectors are combined by an exact all-reduce: bitwise the single-process value.
         One host sync (the returned float)."""
         from sympa_amd import distributed as sd
+        from sympa_amd.graph import WeightedGraphDistances
         man = self.manifold
         table = self.embeddings.embeds.detach()
         dev = table.device
@@ -406,14 +410,18 @@ class Model(nn.Module):
         if gd.device != dev:
             raise ValueError(f"the graph distances live on {gd.device}, the table on {dev}")
         spd = man.model_name == "spd"
-        row_bytes = (4 + 8 + (32 if spd else 0)) * N          # spd: + the [N, 2] pair list and the arange repeats behind it
+        # a WeightedGraphDistances differs in the dtype of the graph rows and in the kernel that reduces them; the rest is shared
+        weighted = isinstance(gd, WeightedGraphDistances)
+        reduce_rows = ops.graph_weighted_distortion_rows if weighted else ops.graph_distortion_rows
+        # spd: + the [N, 2] pair list and the arange repeats behind it
+        row_bytes = ((8 if weighted else 4) + 8 + (32 if spd else 0)) * N
         R = max(64, (int(max_block_bytes) // row_bytes) // 64 * 64)
         begin, count = (0, N) if group is None and not sd.dist.is_initialized() else sd.row_shard(N, group)
         R = min(R, max(count, 1))
         sums = torch.zeros(N, dtype=torch.float64, device=dev)
         pairs = torch.zeros(N, dtype=torch.int64, device=dev)
         if count > 0:
-            hbuf = torch.empty(R, N, dtype=torch.int32, device=dev)
+            hbuf = torch.empty(R, N, dtype=torch.float64 if weighted else torch.int32, device=dev)
             if not spd:
                 weights = man.metric.weights if man.metric.kind is MetricType.WEIGHTED_SUM else None
                 need = ops._lib.load().sympa_all_pairs_workspace_bytes(N, table.shape[-1], ops.MODEL_IDS[man.model_name])
@@ -429,7 +437,7 @@ class Model(nn.Module):
                                               self.scale_coef, b, r, out=dbuf[:r], packed=need > 0, workspace=ws,
                                               flags=ops.FLAG_NO_SYMMETRY)
                 hops = gd.rows(b, r, out=hbuf)
-                ops.graph_distortion_rows(rows, hops, b, row_sum=sums[b:b + r], row_pairs=pairs[b:b + r])
+                reduce_rows(rows, hops, b, row_sum=sums[b:b + r], row_pairs=pairs[b:b + r])
         if group is not None or sd.dist.is_initialized():
             sd.allreduce_row_shards(sums, group)
             sd.allreduce_row_shards(pairs, group)

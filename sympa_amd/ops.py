@@ -1650,3 +1650,89 @@ def graph_distortion_rows(dist_rows, hop_rows, row_begin, row_sum=None, row_pair
                                              row_pairs.data_ptr(), _stream())
     _lib.check(rc)
     return row_sum, row_pairs
+
+
+# ---------------------------------------------------------------------------------------------------
+# Weighted graph distances (C-ABI sympa_graph_weighted_rows; reference preprocess.py:108-114) and the distortion of distance
+# rows against them (C-ABI sympa_graph_weighted_distortion_rows; metrics.py:21)
+# ---------------------------------------------------------------------------------------------------
+def graph_weighted_workspace_bytes(num_nodes, src_count):
+    return int(_lib.load().sympa_graph_weighted_workspace_bytes(int(num_nodes), int(src_count)))
+
+
+def graph_weighted_rows(rowptr, cols, weights, src_begin, src_count, out=None, workspace=None):
+    """Weighted shortest-path distances from the sources [src_begin, src_begin + src_count) to every node (C-ABI
+    sympa_graph_weighted_rows) on the current stream.  rowptr int64 [N + 1], cols int32 [E], weights fp64 [E]: a symmetric CSR
+    with non-negative weights on the device (sympa_amd.graph.weighted_graph_csr).  Returns out fp64 [src_count, N]: bit for bit
+    Dijkstra from each source, 0 on the diagonal, +inf for unreachable nodes; every element is written.  workspace: a device
+    tensor of at least graph_weighted_workspace_bytes(N, src_count) bytes (allocated when not given).  A column outside [0, N) is
+    skipped and raises IndexError from check_status(); a NaN, negative or infinite weight is skipped and raises AssertionError."""
+    lib = _lib.load()
+    _need_gpu(rowptr, "rowptr")
+    _need_gpu(cols, "cols")
+    _need_gpu(weights, "weights")
+    dev = rowptr.device
+    if cols.device != dev or weights.device != dev or rowptr.dtype != torch.int64 or cols.dtype != torch.int32 or \
+            weights.dtype != torch.float64 or rowptr.dim() != 1 or cols.dim() != 1 or weights.shape != cols.shape:
+        raise ValueError("the CSR must be (int64 rowptr [N + 1], int32 cols [E], float64 weights [E]) on one device")
+    rowptr, cols, weights = rowptr.contiguous(), cols.contiguous(), weights.contiguous()
+    N = rowptr.numel() - 1
+    src_begin, src_count = int(src_begin), int(src_count)
+    if out is None:
+        out = torch.empty(max(src_count, 0), max(N, 0), dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or out.device != dev or out.dim() != 2 or out.shape[0] < src_count or out.shape[1] != N or \
+            out.stride(1) != 1 or (out.shape[0] > 1 and out.stride(0) < N):
+        raise ValueError(f"out must be a float64 [>= {src_count}, {N}] tensor with unit column stride on the CSR's device")
+    need = lib.sympa_graph_weighted_workspace_bytes(N, src_count)
+    if workspace is None:
+        workspace = torch.empty(max(need // 8, 1), dtype=torch.int64, device=dev)
+    elif workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError("workspace must be a contiguous tensor on the CSR's device")
+    stride = out.stride(0) if out.shape[0] > 1 else N
+    st = _status_buf(dev)
+    with torch.cuda.device(dev):
+        rc = lib.sympa_graph_weighted_rows(rowptr.data_ptr(), cols.data_ptr() if cols.numel() else None,
+                                           weights.data_ptr() if weights.numel() else None, N, cols.numel(), src_begin,
+                                           src_count, out.data_ptr(), stride, workspace.data_ptr(),
+                                           workspace.numel() * workspace.element_size(), st.data_ptr(), _stream())
+    _lib.check(rc)
+    if _debug:
+        check_status(dev)
+    return out[:src_count]
+
+
+def graph_weighted_sweeps(workspace, num_nodes, src_count):
+    """int64 [src_count] view into the workspace of the last graph_weighted_rows(..., src_count, workspace=workspace) call over a
+    graph of num_nodes nodes: the number of relaxation sweeps the workgroup of each source ran (the word per source behind the
+    planes; include/sympa_hip.h).  For timing tools."""
+    padded = -(-int(src_count) // 8) * 8
+    return workspace.view(torch.int64)[padded * int(num_nodes):padded * int(num_nodes) + int(src_count)]
+
+
+def graph_weighted_distortion_rows(dist_rows, gdist_rows, row_begin, row_sum=None, row_pairs=None):
+    """Per-row distortion sums of rows [row_begin, row_begin + R) (C-ABI sympa_graph_weighted_distortion_rows): row_sum[r] = sum
+    over the columns j > row_begin + r with 0 < gdist_rows[r, j] < inf of |dist_rows[r, j] - g| / g, row_pairs[r] their number.
+    dist_rows and gdist_rows (graph_weighted_rows) fp64 [R, N], unit column strides.  Returns (row_sum fp64 [R], row_pairs
+    int64 [R])."""
+    lib = _lib.load()
+    _need_gpu(dist_rows, "dist_rows")
+    _need_gpu(gdist_rows, "gdist_rows")
+    dev = dist_rows.device
+    if dist_rows.dtype != torch.float64 or gdist_rows.dtype != torch.float64 or dist_rows.dim() != 2 or \
+            dist_rows.shape != gdist_rows.shape or gdist_rows.device != dev or dist_rows.stride(1) != 1 or \
+            gdist_rows.stride(1) != 1:
+        raise ValueError("dist_rows and gdist_rows must be float64 [R, N] tensors of one shape and device with unit column stride")
+    R, N = dist_rows.shape
+    if row_sum is None:
+        row_sum = torch.empty(R, dtype=torch.float64, device=dev)
+    if row_pairs is None:
+        row_pairs = torch.empty(R, dtype=torch.int64, device=dev)
+    for t, dt, name in ((row_sum, torch.float64, "row_sum"), (row_pairs, torch.int64, "row_pairs")):
+        if t.dtype != dt or t.device != dev or t.numel() != R or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} [R] tensor on the rows' device")
+    with torch.cuda.device(dev):
+        rc = lib.sympa_graph_weighted_distortion_rows(dist_rows.data_ptr(), dist_rows.stride(0) if R > 1 else N,
+                                                      gdist_rows.data_ptr(), gdist_rows.stride(0) if R > 1 else N,
+                                                      int(row_begin), R, N, row_sum.data_ptr(), row_pairs.data_ptr(), _stream())
+    _lib.check(rc)
+    return row_sum, row_pairs

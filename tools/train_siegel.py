@@ -4,6 +4,7 @@ rewrite of them: SURVEY 8f): graph -> triplets -> Model -> fused training step -
 
     python tools/train_siegel.py --graph grid3d-125 --manifold upper --metric riem --dims 2 --epochs 50
     python tools/train_siegel.py --graph product-cartesian-45500 --dims 8 --sampled-pairs 1048576 --batch_size 262144
+    python tools/train_siegel.py --edges data/usca312/usca312.edges --dims 3 --epochs 50
 
 Per batch it runs exactly two kernels: sympa_model_loss_backward (forward + AverageDistortionLoss + backward +
 scatter, runner.py:101-105) and sympa_rsgd_step (geoopt RiemannianSGD, train.py:66-68), plus the gradient clip
@@ -17,6 +18,7 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import networkx as nx  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -44,15 +46,31 @@ def train(args, log=print):
         dist.init_process_group("nccl", device_id=dev)
     torch.manual_seed(args.seed)
     hops = None
+    edges = getattr(args, "edges", None)
+    if edges and args.graph != parser().get_default("graph"):
+        raise SystemExit("--edges and --graph name two graphs: give one of them")
+    graph = data.load_edges(edges) if edges else data.named_graph(args.graph)
+    # an .edges file with a weight on every line (preprocess.py:108: nx.is_weighted) trains on weighted shortest-path distances:
+    # fp64 labels from sympa_amd.graph.WeightedGraphDistances, triplets [T, 3] kept as fp64 (node ids are exact in it)
+    weighted = bool(edges) and nx.is_weighted(graph)
     if getattr(args, "sampled_pairs", 0):
         # graphs whose triplets cannot be listed (product-cartesian-45500: 1.035e9): every epoch draws fresh pairs and labels
-        # them with their hop distances on the device; the evaluation streams all pairs in row blocks
-        from sympa_amd.graph import GraphDistances, graph_csr
-        rowptr, cols, id2node = graph_csr(data.named_graph(args.graph))
-        hops = GraphDistances(rowptr, cols, device=dev)
+        # them with their graph distances on the device; the evaluation streams all pairs in row blocks
+        from sympa_amd.graph import GraphDistances, WeightedGraphDistances, graph_csr, weighted_graph_csr
+        if weighted:
+            rowptr, cols, edge_weights, id2node = weighted_graph_csr(graph)
+            hops = WeightedGraphDistances(rowptr, cols, edge_weights, device=dev)
+        else:
+            rowptr, cols, id2node = graph_csr(graph)
+            hops = GraphDistances(rowptr, cols, device=dev)
         trip = None
+    elif weighted:
+        from sympa_amd.graph import WeightedGraphDistances, weighted_graph_csr
+        rowptr, cols, edge_weights, id2node = weighted_graph_csr(graph)
+        pair_ids, pair_dist = WeightedGraphDistances(rowptr, cols, edge_weights, device=dev).triplets()
+        trip = torch.cat((pair_ids.to(torch.float64), pair_dist[:, None]), 1).cpu()
     else:
-        trip, id2node = data.graph_triplets(data.named_graph(args.graph))
+        trip, id2node = data.graph_triplets(graph)
     args.num_points = len(id2node)
     model = Model(args).to(dev)
     if args.optim == "radam":        # train.py:69-70
@@ -60,7 +78,7 @@ def train(args, log=print):
     else:                            # train.py:66-68
         opt = RiemannianSGD(model.parameters(), lr=args.learning_rate * world, weight_decay=0.0, stabilize=None)
     if hops is None:
-        ids_all = trip[:, :2].contiguous().to(dev)
+        ids_all = trip[:, :2].to(torch.int64).contiguous().to(dev)
         gd_all = trip[:, 2].to(torch.float64).to(dev)
     batch = max(1, args.batch_size // world)
     history = []
@@ -102,7 +120,8 @@ def train(args, log=print):
             ids = data.sample_pairs(args.num_points, per_rank, batch_id=(epoch - 1) * world + rank, seed=args.seed).to(dev)
             d = hops.pairs(ids)
             keep = torch.isfinite(d)                      # a pair across two components has no distance to learn
-            mine = torch.cat((ids[keep], d[keep].to(torch.int64)[:, None]), 1)
+            mine = torch.cat((ids[keep].to(d.dtype), d[keep][:, None]), 1) if weighted else \
+                torch.cat((ids[keep], d[keep].to(torch.int64)[:, None]), 1)
         else:
             mine = shard_triplets(trip, rank, world, epoch=epoch, seed=0).to(dev)
         # inside every batch: pairs with the same source row adjacent (free for SGD) -- load_epoch of the replayed steps sorts
@@ -130,9 +149,9 @@ def train(args, log=print):
         for s in range(first, mine.shape[0], batch):
             b = mine[s:s + batch]
             if graphed is not None:
-                graphed(b[:, :2], b[:, 2].to(torch.float64))        # accumulates into graphed.loss
+                graphed(b[:, :2].to(torch.int64), b[:, 2].to(torch.float64))        # accumulates into graphed.loss
                 continue
-            ids, gd = b[:, :2].contiguous(), b[:, 2].to(torch.float64)
+            ids, gd = b[:, :2].to(torch.int64).contiguous(), b[:, 2].to(torch.float64)
             if ex is None:
                 opt.zero_grad(set_to_none=False)
                 loss_sum += model.fused_loss_backward(ids, gd)
@@ -177,6 +196,10 @@ def train(args, log=print):
 def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--graph", default="grid3d-125")
+    ap.add_argument("--edges", default=None, metavar="PATH",
+                    help="train on the graph of an .edges file (data.load_edges: 'src dst [weight]' per line) instead of a named "
+                         "--graph.  With a weight on every line the distances are weighted shortest paths computed on the device "
+                         "(sympa_amd.graph.WeightedGraphDistances), otherwise hop counts; --sampled-pairs works with both")
     ap.add_argument("--manifold", default="upper")
     ap.add_argument("--metric", default="riem")
     ap.add_argument("--dims", type=int, default=2)
