@@ -608,6 +608,40 @@ int sympa_graph_weighted_distortion_rows(const double* dist, int64_t ld_dist, co
                                          int64_t row_begin, int64_t row_count, int64_t num_nodes, double* row_sum,
                                          int64_t* row_pairs, void* stream);
 
+/* Census, ball sizes and ball selection over a block of graph distance rows that is already on the device (csrc/graph_census.hip):
+ * what the reference's --subsample and --scale_triplets (train.py:86-93, utils.py:71-102) need from a graph whose triplets cannot
+ * be listed.  Row r of a block stands for node i = row_begin + r and only its columns j > i count: the pairs a triplet list
+ * holds.  Integer sums only: no result depends on the grid or on how the rows are split into calls.  Arguments are validated
+ * before any launch; row_count == 0 (or m == 0) is a no-op that returns 0.
+ *
+ * sympa_graph_hop_census_rows: the histogram behind d_max (utils.py:71-82) and behind the distance below which a fraction of the
+ * triplets lies (utils.py:85-102).  hops [row_count, ld] int32 (sympa_graph_hop_rows), ld >= num_nodes.
+ *   bins[d] += the number of (r, j) with j > row_begin + r and hops[r][j] == d, for 0 < d < num_bins; values >= num_bins are added
+ *   to bins[0], an overflow counter (distance 0 and unreachable entries are never counted).  bins [num_bins] int64 ACCUMULATES:
+ *   the caller zeroes it.  Each workgroup keeps the first SYMPA_GRAPH_CENSUS_LDS_BINS bins in LDS and flushes them with 64-bit
+ *   global atomics; larger distances go to the global bins directly. */
+#define SYMPA_GRAPH_CENSUS_LDS_BINS 512
+int sympa_graph_hop_census_rows(const int32_t* hops, int64_t ld, int64_t row_begin, int64_t row_count, int64_t num_nodes,
+                                int64_t* bins, int64_t num_bins, void* stream);
+
+/* The ball of radius `radius` (utils.py:85-102: "the local neighbourhood of each node"), row by row:
+ *   upper_count[r] = #{j > row_begin + r : 0 < rows[r][j] <= radius}      (int64 [row_count], written, not accumulated)
+ * rows [row_count, ld]: int32 hop rows (rows_fp64 == 0) or fp64 weighted rows (rows_fp64 == 1; +inf marks an unreachable node).
+ * A NaN, negative or infinite radius is SYMPA_ERR_BAD_ARG. */
+int sympa_graph_ball_count_rows(const void* rows, int rows_fp64, int64_t ld, int64_t row_begin, int64_t row_count,
+                                int64_t num_nodes, double radius, int64_t* upper_count, void* stream);
+
+/* Elements of that ball by (row, rank) (the draw of utils.py:85-102's subsample without its list).  Request k: i = req_row[k], a
+ * global row id inside [row_begin, row_begin + row_count), in any order, repeats allowed;
+ *   out_col[k]  = the column j > i of the ball that has exactly req_rank[k] ball columns strictly between i and j
+ *   out_dist[k] = rows[i - row_begin][j] as fp64 (out_dist may be NULL)
+ * A row outside the block or a rank >= upper_count of its row writes -1 (NaN for the distance) and sets SYMPA_ST_BAD_INDEX in
+ * `status` (word 1 counts the requests; `status` may be NULL).  A wave answers a run of consecutive requests and keeps its place
+ * in a row between them, so requests sorted by (row, rank) cost one scan of a row per wave; any order is answered. */
+int sympa_graph_ball_select_rows(const void* rows, int rows_fp64, int64_t ld, int64_t row_begin, int64_t row_count,
+                                 int64_t num_nodes, double radius, const int64_t* req_row, const int64_t* req_rank, int64_t m,
+                                 int64_t* out_col, double* out_dist, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,9 @@ SYMBOLS = (
     "sympa_graph_weighted_workspace_bytes",
     "sympa_graph_weighted_rows",
     "sympa_graph_weighted_distortion_rows",
+    "sympa_graph_hop_census_rows",
+    "sympa_graph_ball_count_rows",
+    "sympa_graph_ball_select_rows",
 )
 
 _c_double_p = ctypes.c_void_p
@@ -331,6 +334,15 @@ def load():
     lib.sympa_graph_weighted_distortion_rows.restype = C.c_int
     lib.sympa_graph_weighted_distortion_rows.argtypes = [_c_double_p, C.c_int64, _c_double_p, C.c_int64, C.c_int64, C.c_int64,
                                                          C.c_int64, _c_double_p, _c_i64_p, C.c_void_p]
+    lib.sympa_graph_hop_census_rows.restype = C.c_int
+    lib.sympa_graph_hop_census_rows.argtypes = [_c_i32_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _c_i64_p, C.c_int64,
+                                                C.c_void_p]
+    lib.sympa_graph_ball_count_rows.restype = C.c_int
+    lib.sympa_graph_ball_count_rows.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double,
+                                                _c_i64_p, C.c_void_p]
+    lib.sympa_graph_ball_select_rows.restype = C.c_int
+    lib.sympa_graph_ball_select_rows.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double,
+                                                 _c_i64_p, _c_i64_p, C.c_int64, _c_i64_p, _c_double_p, _c_i32_p, C.c_void_p]
     _lib = lib
     return lib
 

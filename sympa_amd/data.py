@@ -213,6 +213,37 @@ def scale_triplet_distances(distances):
     return sq / sq.max()
 
 
+def subsample_triplets(ids_or_triplets, distances, fraction):
+    """utils.subsample_triplets (sympa/utils.py:85-102, train.py:86-89): the K = round(T * fraction) triplets with the SHORTEST
+    graph distances, "the local neighbourhood of each node".  Ties are broken by position in the list (a stable sort) and the
+    result is returned in list order, so a lexicographic list stays lexicographic.  Takes the int64 [T, 3] form
+    (subsample_triplets(triplets, None, F) -> triplets [K, 3]) and the (ids [T, 2], fp64 distances [T]) form
+    (-> (ids [K, 2], distances [K])).  K == 0 raises ValueError.
+
+    This is what the reference's docstring says, not what its code does: it calls np.argpartition(distances, 4), which partitions
+    around the FIFTH smallest element only, so beyond the five smallest distances its selection is in no defined order.  That
+    defect is not reproduced here."""
+    trip = torch.as_tensor(ids_or_triplets)
+    fraction = float(fraction)
+    if not (0.0 < fraction <= 1.0):
+        raise ValueError(f"the fraction must lie in (0, 1], got {fraction!r}")
+    if distances is None:
+        if trip.dim() != 2 or trip.shape[1] < 3:
+            raise ValueError(f"triplets must be [T, 3] when no distances are given, got {tuple(trip.shape)}")
+        dist = trip[:, 2]
+    else:
+        dist = torch.as_tensor(distances)
+        if dist.dim() != 1 or dist.shape[0] != trip.shape[0]:
+            raise ValueError(f"{trip.shape[0]} pairs but distances of shape {tuple(dist.shape)}")
+    K = round(trip.shape[0] * fraction)
+    if K == 0:
+        raise ValueError(f"the fraction {fraction!r} of {trip.shape[0]} triplets keeps none")
+    keep = torch.sort(torch.argsort(dist, stable=True)[:K]).values
+    if distances is None:
+        return trip[keep]
+    return trip[keep], dist[keep]
+
+
 def save_checkpoint(path, model, id2node):
     """runner.py:156-160: {"model": ddp_model.state_dict(), "id2node": ...}; DDP prefixes keys with "module."."""
     state = {f"module.{k}": v.detach().cpu() for k, v in model.state_dict().items()}

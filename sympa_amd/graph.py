@@ -15,7 +15,15 @@ fp64 rows: weighted_graph_csr, host_weighted_rows and WeightedGraphDistances (cs
 ops.graph_weighted_rows).  A row is the left-to-right fp64 sum of the lightest path FROM ITS OWN SOURCE, bit for bit what Dijkstra
 from that source computes; rows i and j may therefore disagree about the pair (i, j) in the last bits, and nothing here
 symmetrises them (the reference keeps shortest_paths[i][j] with i < j, taken from row i).
+
+The reference's --subsample and --scale_triplets (train.py:86-93, utils.py:71-102) need the list of all triplets; for graphs that
+cannot list them the same row blocks are reduced on the device (csrc/graph_census.hip through ops.graph_hop_census_rows,
+graph_ball_count_rows and graph_ball_select_rows): GraphDistances.census / radius_for_fraction / ball_sizes / sample_ball_pairs,
+their numpy restatements host_hop_census / host_ball_counts / host_ball_select, and ScaledGraphDistances for scaled labels.
 """
+from collections import namedtuple
+
+
 import numpy as np
 import torch
 
@@ -84,6 +92,64 @@ def host_hop_rows(rowptr, cols, begin, count):
             block[((fresh[None, :] >> shifts[:nbits]) & np.uint64(1)).astype(bool)] = level
             cur = fresh
     return out
+
+
+def _ball_mask(rows, row_begin, radius):
+    """bool [R, N]: column j of row r is in the ball when j > row_begin + r and 0 < rows[r, j] <= radius."""
+    rows = np.asarray(rows.cpu() if torch.is_tensor(rows) else rows)
+    radius = float(radius)
+    if not (0.0 <= radius < np.inf):
+        raise ValueError(f"the radius must be finite and not negative, got {radius!r}")
+    R, N = rows.shape
+    upper = np.arange(N)[None, :] > (int(row_begin) + np.arange(R))[:, None]
+    with np.errstate(invalid="ignore"):
+        return rows, upper & (rows > 0) & (rows.astype(np.float64) <= radius)
+
+
+def host_hop_census(hop_rows, row_begin, num_bins):
+    """int64 [num_bins] ndarray, the numpy restatement of ops.graph_hop_census_rows over zeroed bins: bin d counts the (r, j)
+    with j > row_begin + r and hop_rows[r, j] == d for 0 < d < num_bins, bin 0 the values >= num_bins."""
+    rows = np.asarray(hop_rows.cpu() if torch.is_tensor(hop_rows) else hop_rows)
+    num_bins = int(num_bins)
+    if num_bins < 1:
+        raise ValueError("num_bins must be at least 1")
+    R, N = rows.shape
+    upper = np.arange(N)[None, :] > (int(row_begin) + np.arange(R))[:, None]
+    v = rows[upper & (rows > 0)].astype(np.int64)
+    return np.bincount(np.where(v < num_bins, v, 0), minlength=num_bins).astype(np.int64)
+
+
+def host_ball_counts(rows, row_begin, radius):
+    """int64 [R] ndarray, the numpy restatement of ops.graph_ball_count_rows: #{j > row_begin + r : 0 < rows[r, j] <= radius}."""
+    return _ball_mask(rows, row_begin, radius)[1].sum(1).astype(np.int64)
+
+
+def host_ball_select(rows, row_begin, radius, req_row, req_rank):
+    """(col int64 [m], dist fp64 [m]) ndarrays, the numpy restatement of ops.graph_ball_select_rows: for request k the column of
+    the ball of row req_row[k] (a global row id) with exactly req_rank[k] ball columns below it, and that entry; -1 and NaN for a
+    row outside the block or a rank the row's ball does not have."""
+    rows, mask = _ball_mask(rows, row_begin, radius)
+    R = rows.shape[0]
+    r = _as_numpy(req_row, np.int64) - int(row_begin)
+    rank = _as_numpy(req_rank, np.int64)
+    counts = mask.sum(1).astype(np.int64)
+    first = np.cumsum(counts) - counts
+    at_row, at_col = np.nonzero(mask)                                     # row-major: each row's ball columns ascending
+    inside = (r >= 0) & (r < R)
+    rc = np.where(inside, r, 0)
+    ok = inside & (rank >= 0) & (rank < (counts[rc] if R else 0))
+    pos = np.where(ok, (first[rc] if R else 0) + rank, 0)
+    col = np.full(r.shape, -1, dtype=np.int64)
+    dist = np.full(r.shape, np.nan, dtype=np.float64)
+    if ok.any():
+        col[ok] = at_col[pos[ok]]
+        dist[ok] = rows[rc[ok], col[ok]].astype(np.float64)
+    return col, dist
+
+
+# GraphDistances.census(): histogram int64 [diameter + 1] (CPU tensor; h[d] = #{i < j : d(i, j) = d}, h[0] = 0), triplets = sum h =
+# count_triplets(), diameter = the largest d with h[d] > 0 (0 for a graph without an edge)
+HopCensus = namedtuple("HopCensus", ("histogram", "triplets", "diameter"))
 
 
 class GraphDistances:
@@ -214,6 +280,100 @@ class GraphDistances:
             r, j = torch.nonzero((rows > 0) & (col[None, :] > i[:, None]), as_tuple=True)      # row-major: lexicographic
             parts.append(torch.stack((r + b, j, rows[r, j].to(torch.int64)), 1))
         return torch.cat(parts) if parts else torch.zeros(0, 3, dtype=torch.int64, device=self.device)
+
+    # -----------------------------------------------------------------------------------------------
+    # The short-distance part of the triplet list without the list (train.py:86-93, utils.py:71-102)
+    # -----------------------------------------------------------------------------------------------
+    def census(self):
+        """HopCensus(histogram, triplets, diameter): how many pairs i < j lie at every hop distance.  One pass over blocks(),
+        each block reduced by ops.graph_hop_census_rows into N bins on the device (a hop distance is at most N - 1), one host
+        sync at the end; the histogram is trimmed to [diameter + 1].  The maximum utils.scale_triplets divides by is `diameter`,
+        the cut of utils.subsample_triplets comes from radius_for_fraction."""
+        N = self.num_nodes
+        bins = torch.zeros(N, dtype=torch.int64, device=self.device)
+        for b, rows in self.blocks():
+            if rows.is_cuda:
+                from sympa_amd import ops
+                ops.graph_hop_census_rows(rows, b, bins)
+            else:
+                bins += torch.from_numpy(host_hop_census(rows, b, N))
+        h = bins.cpu()
+        if int(h[0]) != 0:
+            raise AssertionError(f"{int(h[0])} hop distances of {N} and more in a graph of {N} nodes")
+        nz = torch.nonzero(h).flatten()
+        diameter = int(nz[-1]) if nz.numel() else 0
+        return HopCensus(h[:diameter + 1].clone(), int(h.sum()), diameter)
+
+    def radius_for_fraction(self, fraction, census=None):
+        """(r_F, |S_{r_F}|): the smallest distance r with at least K = round(T * fraction) pairs i < j at 0 < d <= r (Python's
+        round, as utils.py:96), and the number of pairs of that ball.  Hop distances are massively tied, so the ball keeps every
+        pair at the threshold distance: |S_r| >= K.  `census`: a census() result to reuse.  K == 0 raises ValueError."""
+        fraction = float(fraction)
+        if not (0.0 < fraction <= 1.0):
+            raise ValueError(f"the fraction must lie in (0, 1], got {fraction!r}")
+        c = self.census() if census is None else census
+        K = round(c.triplets * fraction)
+        if K == 0:
+            raise ValueError(f"the fraction {fraction!r} of {c.triplets} triplets keeps none")
+        cum = torch.cumsum(c.histogram, 0)
+        r = int(torch.searchsorted(cum, torch.tensor(K, dtype=torch.int64)))
+        return r, int(cum[r])
+
+    def ball_sizes(self, radius):
+        """int64 [N] on the device: u[i] = #{j > i : 0 < d(i, j) <= radius}, one pass over blocks() through
+        ops.graph_ball_count_rows.  Its sum is the size of the ball S_radius."""
+        upper = torch.empty(self.num_nodes, dtype=torch.int64, device=self.device)
+        for b, rows in self.blocks():
+            if rows.is_cuda:
+                from sympa_amd import ops
+                ops.graph_ball_count_rows(rows, b, radius, upper_count=upper[b:b + rows.shape[0]])
+            else:
+                upper[b:b + rows.shape[0]] = torch.from_numpy(host_ball_counts(rows, b, radius))
+        return upper
+
+    def sample_ball_pairs(self, radius, batch, batch_id=0, seed=42, upper=None):
+        """(ids int64 [batch, 2], dist fp64 [batch]) on the device: `batch` draws, with replacement, from the ball
+        S_radius = {(i, j) : i < j, 0 < d(i, j) <= radius} in lexicographic order.  Draw m of batch `batch_id` is element number
+        data.keyed_u64(seed, 12, batch_id * batch + m) mod |S_radius| and fills output row m.  The element numbers are turned into
+        (row, rank inside the row's ball) by a searchsorted on the prefix sum of ball_sizes(radius), the requests are grouped by
+        the block of their row as pairs() groups them, every needed block is computed once and answered by
+        ops.graph_ball_select_rows.  Nothing in the result depends on the block size.  `upper`: a ball_sizes(radius) result to
+        reuse across epochs.  An empty ball raises ValueError."""
+        from sympa_amd import data
+        batch = int(batch)
+        upper = self.ball_sizes(radius) if upper is None else upper.to(self.device)
+        N = self.num_nodes
+        prefix = torch.cumsum(upper, 0)
+        size = int(prefix[-1])
+        if size <= 0:
+            raise ValueError(f"no pair of the graph lies within the radius {radius!r}")
+        cnt = np.uint64(int(batch_id)) * np.uint64(batch) + np.arange(batch, dtype=np.uint64)
+        k = torch.from_numpy((data.keyed_u64(seed, 12, cnt) % np.uint64(size)).astype(np.int64)).to(self.device)
+        row = torch.searchsorted(prefix, k, right=True)                   # the first row whose prefix exceeds k
+        rank = k - (prefix[row] - upper[row])
+        ids = torch.empty(batch, 2, dtype=torch.int64, device=self.device)
+        dist = torch.empty(batch, dtype=torch.float64, device=self.device)
+        if batch == 0:
+            return ids, dist
+        buf = self._block_buffer()
+        R = buf.shape[0]
+        order = torch.argsort(k)                                          # by element number: by (row, rank), the order the kernel likes
+        row_s, rank_s = row[order].contiguous(), rank[order].contiguous()
+        needed, counts = torch.unique_consecutive(row_s // R, return_counts=True)
+        start = 0
+        for blk, end in zip(needed.tolist(), torch.cumsum(counts, 0).tolist()):
+            b = blk * R
+            rows = self.rows(b, min(R, N - b), out=buf)
+            if rows.is_cuda:
+                from sympa_amd import ops
+                col, d = ops.graph_ball_select_rows(rows, b, radius, row_s[start:end], rank_s[start:end])
+            else:
+                col, d = (torch.from_numpy(x) for x in host_ball_select(rows, b, radius, row_s[start:end], rank_s[start:end]))
+            ids[order[start:end], 1] = col
+            dist[order[start:end]] = d
+            start = end
+        ids[:, 0] = row
+        return ids, dist
 
     def neighbor_csr(self):
         """(rowptr int64 [N + 1], cols int32 [E]) of the hop-1 neighbour sets, rows ascending and unique: what ops.map_rows and
@@ -442,3 +602,75 @@ class WeightedGraphDistances(GraphDistances):
         rowptr = torch.zeros(N + 1, dtype=torch.int64, device=self.device)
         rowptr[1:] = torch.cumsum(torch.bincount(r, minlength=N), 0)
         return rowptr, (key - r * N).to(torch.int32)
+
+    def census(self):
+        raise NotImplementedError("a census has one bin per hop distance: weighted distances have diameter(), ball_sizes(radius) "
+                                  "and radius_for_fraction(F) over the listed triplets")
+
+    def diameter(self):
+        """The largest finite distance D[i][j] (one pass over every row block); what utils.scale_triplets divides by."""
+        top = torch.zeros((), dtype=torch.float64, device=self.device)
+        for b, rows in self.blocks():
+            top = torch.maximum(top, torch.where(torch.isfinite(rows), rows, torch.zeros_like(rows)).max())
+        return float(top)
+
+    def radius_for_fraction(self, fraction, max_bytes=TRIPLETS_MAX_BYTES):
+        """(r_F, |S_{r_F}|): the exact K-th smallest listed distance, K = round(T * fraction) (Python's round, utils.py:96), and
+        the number of listed pairs at 0 < d <= r_F (>= K where distances tie).  It lists the triplets, so they must fit
+        max_bytes: a larger graph raises MemoryError and takes an explicit radius (ball_sizes(radius),
+        sample_ball_pairs(radius, ...)) instead; no streamed fp64 quantile is built.  K == 0 raises ValueError."""
+        fraction = float(fraction)
+        if not (0.0 < fraction <= 1.0):
+            raise ValueError(f"the fraction must lie in (0, 1], got {fraction!r}")
+        try:
+            _, dist = self.triplets(max_bytes=max_bytes)
+        except MemoryError as e:
+            raise MemoryError(f"radius_for_fraction lists the weighted triplets and they do not fit ({e}); "
+                              "give an explicit radius to ball_sizes / sample_ball_pairs instead") from None
+        K = round(dist.numel() * fraction)
+        if K == 0:
+            raise ValueError(f"the fraction {fraction!r} of {dist.numel()} triplets keeps none")
+        r = float(torch.kthvalue(dist, K).values)
+        return r, int((dist <= r).sum())
+
+
+class ScaledGraphDistances(WeightedGraphDistances):
+    """The labels of utils.scale_triplets (sympa/utils.py:71-82, train.py:91-93) as graph distance rows: rows() returns fp64
+    d^2 / max_distance^2 of the wrapped GraphDistances' or WeightedGraphDistances' rows (the operations of
+    data.scale_triplet_distances, bit for bit), +inf for unreachable entries, 0 on the diagonal.  Being a WeightedGraphDistances,
+    Model.evaluate_all_pairs scores scaled labels over all pairs through the weighted distortion kernel.  max_distance: the
+    census' diameter (hops) or diameter() (weighted) for the reference's labels."""
+
+    def __init__(self, gd, max_distance):
+        max_distance = float(max_distance)
+        if not (0.0 < max_distance < float("inf")):
+            raise ValueError(f"max_distance must be positive and finite, got {max_distance!r}")
+        self.base, self.max_distance = gd, max_distance
+        self.device, self.num_nodes = gd.device, gd.num_nodes
+        self.rowptr, self.cols, self.weights = gd.rowptr, gd.cols, getattr(gd, "weights", None)
+        self.max_block_bytes = gd.max_block_bytes
+        self.block_rows = self.rows_per_block(self.max_block_bytes)
+        self._buf = self._ws = None
+
+    def rows(self, begin, count, out=None):
+        """fp64 [count, N]: d^2 / max_distance^2 of the wrapped rows [begin, begin + count).  The wrapped rows pass through the
+        wrapped object's own block buffer where they fit it."""
+        base = self.base
+        buf = base._block_buffer()
+        src = base.rows(begin, count, out=buf if int(count) <= buf.shape[0] else None)
+        d = src.to(torch.float64)
+        scaled = (d * d) / (self.max_distance * self.max_distance)
+        if not src.is_floating_point():
+            scaled = torch.where(src < 0, torch.full_like(scaled, float("inf")), scaled)
+        if out is None:
+            return scaled
+        out[:int(count)].copy_(scaled)
+        return out[:int(count)]
+
+    def release(self):
+        self._buf = self._ws = None
+        self.base.release()
+
+    def neighbor_csr(self):
+        """The wrapped graph's neighbour sets: scaling the labels does not change who is a neighbour."""
+        return self.base.neighbor_csr()

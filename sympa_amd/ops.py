@@ -1736,3 +1736,93 @@ def graph_weighted_distortion_rows(dist_rows, gdist_rows, row_begin, row_sum=Non
                                                       int(row_begin), R, N, row_sum.data_ptr(), row_pairs.data_ptr(), _stream())
     _lib.check(rc)
     return row_sum, row_pairs
+
+
+# ---------------------------------------------------------------------------------------------------
+# Census, ball sizes and ball selection over graph distance rows (C-ABI sympa_graph_hop_census_rows, sympa_graph_ball_count_rows,
+# sympa_graph_ball_select_rows; reference train.py:86-93, utils.py:71-102)
+# ---------------------------------------------------------------------------------------------------
+def _graph_rows(rows, name):
+    """(R, N, leading dimension, fp64 flag) of a block of graph distance rows: int32 (graph_hop_rows) or float64
+    (graph_weighted_rows), [R, N] with unit column stride."""
+    _need_gpu(rows, name)
+    if rows.dtype not in (torch.int32, torch.float64) or rows.dim() != 2 or rows.stride(1) != 1 or \
+            (rows.shape[0] > 1 and rows.stride(0) < rows.shape[1]):
+        raise ValueError(f"{name} must be an int32 or float64 [R, N] tensor with unit column stride")
+    R, N = rows.shape
+    return R, N, (rows.stride(0) if R > 1 else N), int(rows.dtype == torch.float64)
+
+
+def graph_hop_census_rows(hop_rows, row_begin, bins):
+    """bins[d] += the number of (r, j) with j > row_begin + r and hop_rows[r, j] == d for 0 < d < bins.numel(); larger values are
+    added to bins[0], an overflow counter (C-ABI sympa_graph_hop_census_rows).  hop_rows int32 [R, N] (graph_hop_rows), unit
+    column stride; bins a contiguous int64 vector on the same device that ACCUMULATES: zero it first.  Returns bins."""
+    lib = _lib.load()
+    R, N, ld, fp64 = _graph_rows(hop_rows, "hop_rows")
+    dev = hop_rows.device
+    if fp64:
+        raise ValueError("hop_rows must be int32: a census has one bin per hop distance")
+    if bins.dtype != torch.int64 or bins.device != dev or bins.dim() != 1 or bins.numel() < 1 or not bins.is_contiguous():
+        raise ValueError("bins must be a contiguous int64 vector of at least one element on the rows' device")
+    if R == 0:
+        return bins
+    with torch.cuda.device(dev):
+        rc = lib.sympa_graph_hop_census_rows(hop_rows.data_ptr(), ld, int(row_begin), R, N, bins.data_ptr(), bins.numel(), _stream())
+    _lib.check(rc)
+    return bins
+
+
+def graph_ball_count_rows(rows, row_begin, radius, upper_count=None):
+    """upper_count[r] = #{j > row_begin + r : 0 < rows[r, j] <= radius} (C-ABI sympa_graph_ball_count_rows).  rows int32 [R, N]
+    (graph_hop_rows) or float64 [R, N] (graph_weighted_rows), unit column stride.  Returns upper_count int64 [R]."""
+    lib = _lib.load()
+    R, N, ld, fp64 = _graph_rows(rows, "rows")
+    dev = rows.device
+    if upper_count is None:
+        upper_count = torch.empty(R, dtype=torch.int64, device=dev)
+    elif upper_count.dtype != torch.int64 or upper_count.device != dev or upper_count.numel() != R or not upper_count.is_contiguous():
+        raise ValueError("upper_count must be a contiguous int64 [R] tensor on the rows' device")
+    if R == 0:
+        return upper_count
+    with torch.cuda.device(dev):
+        rc = lib.sympa_graph_ball_count_rows(rows.data_ptr(), fp64, ld, int(row_begin), R, N, float(radius), upper_count.data_ptr(),
+                                             _stream())
+    _lib.check(rc)
+    return upper_count
+
+
+def graph_ball_select_rows(rows, row_begin, radius, req_row, req_rank, out_col=None, out_dist=None):
+    """For request k the column j > req_row[k] of the ball 0 < rows[i - row_begin, j] <= radius with exactly req_rank[k] ball columns
+    between i = req_row[k] and j, and that entry as fp64 (C-ABI sympa_graph_ball_select_rows).  req_row (global row ids inside
+    [row_begin, row_begin + R), any order, repeats allowed) and req_rank: contiguous int64 [m].  Returns (out_col int64 [m],
+    out_dist float64 [m]).  A row outside the block or a rank >= the row's ball size gives -1 / NaN and raises IndexError from
+    check_status()."""
+    lib = _lib.load()
+    R, N, ld, fp64 = _graph_rows(rows, "rows")
+    dev = rows.device
+    for t, name in ((req_row, "req_row"), (req_rank, "req_rank")):
+        if t.dtype != torch.int64 or t.device != dev or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int64 vector on the rows' device")
+    m = req_row.numel()
+    if req_rank.numel() != m:
+        raise ValueError(f"{m} request rows but {req_rank.numel()} ranks")
+    if out_col is None:
+        out_col = torch.empty(m, dtype=torch.int64, device=dev)
+    if out_dist is None:
+        out_dist = torch.empty(m, dtype=torch.float64, device=dev)
+    for t, dt, name in ((out_col, torch.int64, "out_col"), (out_dist, torch.float64, "out_dist")):
+        if t.dtype != dt or t.device != dev or t.numel() != m or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} [m] tensor on the rows' device")
+    if m == 0:
+        return out_col, out_dist
+    if R == 0:
+        raise ValueError("requests against an empty block of rows")
+    st = _status_buf(dev)
+    with torch.cuda.device(dev):
+        rc = lib.sympa_graph_ball_select_rows(rows.data_ptr(), fp64, ld, int(row_begin), R, N, float(radius), req_row.data_ptr(),
+                                              req_rank.data_ptr(), m, out_col.data_ptr(), out_dist.data_ptr(), st.data_ptr(),
+                                              _stream())
+    _lib.check(rc)
+    if _debug:
+        check_status(dev)
+    return out_col, out_dist

@@ -5,6 +5,8 @@ rewrite of them: SURVEY 8f): graph -> triplets -> Model -> fused training step -
     python tools/train_siegel.py --graph grid3d-125 --manifold upper --metric riem --dims 2 --epochs 50
     python tools/train_siegel.py --graph product-cartesian-45500 --dims 8 --sampled-pairs 1048576 --batch_size 262144
     python tools/train_siegel.py --edges data/usca312/usca312.edges --dims 3 --epochs 50
+    python tools/train_siegel.py --graph grid3d-125 --subsample 0.25 --scale_triplets
+    python tools/train_siegel.py --graph product-cartesian-45500 --dims 8 --sampled-pairs 1048576 --batch_size 262144 --subsample 0.01
 
 Per batch it runs exactly two kernels: sympa_model_loss_backward (forward + AverageDistortionLoss + backward +
 scatter, runner.py:101-105) and sympa_rsgd_step (geoopt RiemannianSGD, train.py:66-68), plus the gradient clip
@@ -53,6 +55,16 @@ def train(args, log=print):
     # an .edges file with a weight on every line (preprocess.py:108: nx.is_weighted) trains on weighted shortest-path distances:
     # fp64 labels from sympa_amd.graph.WeightedGraphDistances, triplets [T, 3] kept as fp64 (node ids are exact in it)
     weighted = bool(edges) and nx.is_weighted(graph)
+    # train.py:86-93; read like `edges`, so that a Namespace built by hand without them keeps today's behaviour
+    subsample = float(getattr(args, "subsample", 0.0) or 0.0)
+    scale_labels = bool(getattr(args, "scale_triplets", False))
+    ball_radius = getattr(args, "ball_radius", None)
+    if subsample < 0.0 or subsample > 1.0:
+        raise SystemExit("--subsample takes a fraction in (0, 1]")
+    if ball_radius is not None and not getattr(args, "sampled_pairs", 0):
+        raise SystemExit("--ball-radius names the ball --sampled-pairs draws from: the listed path takes --subsample")
+    if ball_radius is not None and subsample > 0.0:
+        raise SystemExit("--ball-radius and --subsample both choose the radius: give one of them")
     if getattr(args, "sampled_pairs", 0):
         # graphs whose triplets cannot be listed (product-cartesian-45500: 1.035e9): every epoch draws fresh pairs and labels
         # them with their graph distances on the device; the evaluation streams all pairs in row blocks
@@ -77,9 +89,40 @@ def train(args, log=print):
         opt = RiemannianAdam(model.parameters(), lr=args.learning_rate * world, eps=1e-7, stabilize=None)
     else:                            # train.py:66-68
         opt = RiemannianSGD(model.parameters(), lr=args.learning_rate * world, weight_decay=0.0, stabilize=None)
+    radius = upper = None
+    eval_hops = hops
+    label_max = None
     if hops is None:
         ids_all = trip[:, :2].to(torch.int64).contiguous().to(dev)
         gd_all = trip[:, 2].to(torch.float64).to(dev)
+        # train.py:86-89,100-103: train on the shortest fraction of the triplets, validate on all of them
+        train_trip = data.subsample_triplets(trip, None, subsample) if subsample > 0.0 else trip
+        if scale_labels:
+            # train.py:91-93 calls scale_triplets on each list by itself: the training labels are divided by the SUBSAMPLE's own
+            # largest squared distance, the validation labels by the largest of all triplets
+            gd_all = data.scale_triplet_distances(gd_all)
+            train_trip = torch.cat((train_trip[:, :2].to(torch.float64),
+                                    data.scale_triplet_distances(train_trip[:, 2])[:, None]), 1)
+    elif subsample > 0.0 or ball_radius is not None or scale_labels:
+        # once, before the first epoch: the census (hop graphs: d_max and the radius of the fraction) and the ball's row sizes
+        from sympa_amd.graph import ScaledGraphDistances
+        if ball_radius is not None:
+            radius = float(ball_radius)
+        elif subsample > 0.0 and weighted:
+            radius = hops.radius_for_fraction(subsample)[0]
+        census = hops.census() if not weighted and (scale_labels or (subsample > 0.0 and radius is None)) else None
+        if subsample > 0.0 and radius is None:
+            radius = float(hops.radius_for_fraction(subsample, census)[0])
+        if radius is not None:
+            upper = hops.ball_sizes(radius)
+            if rank == 0:
+                log(f"training on the ball of radius {radius:g}: {int(upper.sum())} pairs")
+        if scale_labels:
+            # training labels (d / r)^2: the ball's own maximum, as train.py:91-93 scales the subsample by its own; the evaluation
+            # scores all pairs against (d / d_max)^2
+            diameter = hops.diameter() if weighted else float(census.diameter)
+            label_max = radius if radius is not None else diameter
+            eval_hops = ScaledGraphDistances(hops, diameter)
     batch = max(1, args.batch_size // world)
     history = []
     # single GPU: the whole step is one hipGraph replay
@@ -117,13 +160,19 @@ def train(args, log=print):
     for epoch in range(1, args.epochs + 1):
         if hops is not None:
             per_rank = max(1, args.sampled_pairs // world)
-            ids = data.sample_pairs(args.num_points, per_rank, batch_id=(epoch - 1) * world + rank, seed=args.seed).to(dev)
-            d = hops.pairs(ids)
+            if radius is not None:
+                # pairs of the ball only (every one has a distance), drawn and labelled on the device
+                ids, d = hops.sample_ball_pairs(radius, per_rank, batch_id=(epoch - 1) * world + rank, seed=args.seed, upper=upper)
+            else:
+                ids = data.sample_pairs(args.num_points, per_rank, batch_id=(epoch - 1) * world + rank, seed=args.seed).to(dev)
+                d = hops.pairs(ids)
             keep = torch.isfinite(d)                      # a pair across two components has no distance to learn
-            mine = torch.cat((ids[keep].to(d.dtype), d[keep][:, None]), 1) if weighted else \
+            if label_max is not None:
+                d = (d * d) / (label_max * label_max)
+            mine = torch.cat((ids[keep].to(d.dtype), d[keep][:, None]), 1) if weighted or label_max is not None else \
                 torch.cat((ids[keep], d[keep].to(torch.int64)[:, None]), 1)
         else:
-            mine = shard_triplets(trip, rank, world, epoch=epoch, seed=0).to(dev)
+            mine = shard_triplets(train_trip, rank, world, epoch=epoch, seed=0).to(dev)
         # inside every batch: pairs with the same source row adjacent (free for SGD) -- load_epoch of the replayed steps sorts
         # by itself; only the eager per-batch loop needs it here (one argsort per epoch, not two)
         loads_epoch = dstep is not None or (graphed is not None and graphed.mode == "two_kernels")
@@ -183,7 +232,7 @@ def train(args, log=print):
         if epoch % args.val_every == 0 or epoch == args.epochs:
             torch.cuda.synchronize(dev)
             t_train = time.perf_counter() - t0
-            distortion = model.evaluate_all_pairs(hops) if hops is not None else evaluate(model, ids_all, gd_all, args.batch_size)
+            distortion = model.evaluate_all_pairs(eval_hops) if hops is not None else evaluate(model, ids_all, gd_all, args.batch_size)
             ops.check_status(dev)
             history.append((epoch, float(loss_sum) / max(1, mine.shape[0]), distortion))
             if rank == 0:
@@ -219,6 +268,17 @@ def parser():
                          "on the device (sympa_amd.graph.GraphDistances.pairs), instead of on the list of all triplets; the "
                          "distortion is then taken over all pairs in row blocks (Model.evaluate_all_pairs).  With --graph "
                          "product-cartesian-45500 this trains configs[3] on its own graph")
+    ap.add_argument("--subsample", type=float, default=0.0, metavar="F",
+                    help="train on the fraction F of the triplets with the shortest graph distances (train.py:86-89; "
+                         "data.subsample_triplets) and validate on all of them.  With --sampled-pairs every epoch draws its pairs "
+                         "from the ball of the smallest radius that holds F of the pairs (GraphDistances.radius_for_fraction, "
+                         "sample_ball_pairs)")
+    ap.add_argument("--scale_triplets", action="store_true", default=False,
+                    help="labels (d / d_max)^2 (train.py:91-93; data.scale_triplet_distances): the training labels by the training "
+                         "pairs' own maximum, the validation labels by the maximum of all pairs")
+    ap.add_argument("--ball-radius", dest="ball_radius", type=float, default=None, metavar="R",
+                    help="with --sampled-pairs: draw the pairs from the ball 0 < d <= R instead of deriving the radius from "
+                         "--subsample (for weighted graphs too large to list their triplets)")
     ap.add_argument("--grad_exchange", default="none", choices=["none", "auto", "dense", "rows", "sharded"],
                     help="single GPU: run the step through sympa_amd.distributed.GradientExchange anyway (tests); with "
                          "N > 1 GPUs the exchange is always on and this picks its mode (none = auto)")
