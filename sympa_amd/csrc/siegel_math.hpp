@@ -372,9 +372,37 @@ SYMPA_UNROLL
 // With delta = h_qq - h_pp, r = sqrt(delta^2 + 4 a^2):  cos 2theta = |delta| / r,  sin 2theta = 2 a / r, so
 //   c^2 = (1 + |delta|/r) / 2,   s / a = sgn(delta) / (r c),   t a = a^2 / (r c^2)
 // which needs two reciprocal square roots, no division and no sqrt(a^2), and has no cancellation.
-// The rounds {(0,1),(2,3)}, {(0,2),(1,3)}, ... of the round-robin order touch disjoint index pairs,
-// so their parameter chains are independent instruction streams.
+//
+// n = 4 rotates a whole ROUND of the round-robin order at once (jacobi_round).  The rounds {(0,1),(2,3)},
+// {(0,2),(1,3)}, {(0,3),(1,2)} are two rotations A = (p,q), B = (r,s) on disjoint index pairs: their parameter
+// chains read different entries (independent instruction streams), and the only off-diagonal entries the round
+// changes are the 2 x 2 complex block  M = [[h_pr, h_ps], [h_qr, h_qs]]  <-  J_A^H M J_B.  With the cosine pulled
+// out of each rotation,
+//   J = c T,   T = [[1, tau], [-conj(tau), 1]],   tau = s e^{i phi} / c = (s / (a c)) beta,
+// the block is  (c_A c_B) T_A^H M T_B:  two products of 16 fma each with NO multiply in front of them, then one
+// scalar on the eight results: 1 + 16 + 16 + 8 = 41 instructions where two separate rotations spend 2 * 24 = 48
+// (each has a `c * x` in front of every fma pair).  s / (a c) is the product the diagonal shift t a forms anyway.
+// n = 3 has one row outside each pivot, nothing to share: it keeps the rotation by rotation form, cyclic by rows.
 // ---------------------------------------------------------------------------------------------
+// Parameters of the rotation on pivot (p,q):  c = cos,  tau = (tr, ti),  ua2 = t |beta| (the diagonal shift).
+template <int N>
+SYMPA_HD void jacobi_angle(const Herm<N>& h, const int p, const int q, double& c, double& tr, double& ti, double& ua2) {
+    const double br = h.re[p][q], bi = h.im[p][q];
+    const double a2 = d_fma(br, br, bi * bi);
+    const double delta = h.d[q] - h.d[p];
+    // |delta| + 1e-150 keeps r2 > 0 (and gives c = 1, tau = 0) when beta = delta = 0
+    const double ad = fabs(delta) + 1e-150;
+    const double qr = d_rsqrt(d_fma(ad, ad, 4.0 * a2));      // 1 / r,  r = sqrt(delta^2 + 4 a^2)
+    const double c2 = d_fma(0.5 * ad, qr, 0.5);                // cos^2 = (1 + |delta|/r) / 2
+    const double ic = d_rsqrt(c2);
+    c = c2 * ic;
+    const double cu = copysign(qr, delta) * ic;                // s / a, signed
+    const double uc = cu * ic;                                 // s / (a c)
+    ua2 = uc * a2;                                             // t * |beta|
+    tr = uc * br;
+    ti = uc * bi;
+}
+
 template <int N>
 SYMPA_HD void jacobi_rotate(Herm<N>& h, const int p, const int q) {   // p < q, static after unrolling
         {
@@ -412,12 +440,85 @@ SYMPA_UNROLL
         }
 }
 
+// Element (i, j), i != j, of the Hermitian matrix from / into its stored upper triangle.
 template <int N>
-SYMPA_HD void jacobi_sweep(Herm<N>& h) {
-    if (N == 4) {   // round-robin: 3 rounds of 2 disjoint rotations
-        jacobi_rotate<N>(h, 0, 1); jacobi_rotate<N>(h, 2, 3);
-        jacobi_rotate<N>(h, 0, 2); jacobi_rotate<N>(h, 1, 3);
-        jacobi_rotate<N>(h, 0, 3); jacobi_rotate<N>(h, 1, 2);
+SYMPA_HD void herm_get(const Herm<N>& h, int i, int j, double& re, double& im) {
+    if (i < j) { re = h.re[i][j]; im = h.im[i][j]; } else { re = h.re[j][i]; im = -h.im[j][i]; }
+}
+template <int N>
+SYMPA_HD void herm_set(Herm<N>& h, int i, int j, double re, double im) {
+    if (i < j) { h.re[i][j] = re; h.im[i][j] = im; } else { h.re[j][i] = re; h.im[j][i] = -im; }
+}
+
+// One round of n = 4: the rotations A = (p,q) and B = (r,s), {p,q,r,s} = {0,1,2,3}, p < q, r < s (comment block above).
+// ZEROS: which entries of M = [[h_pr, h_ps], [h_qr, h_qs]] are exact zeros because the round before has just annihilated them
+// (its two pivots always lie in this round's block):  ROUND_FULL none (the very first round),  ROUND_DIAG h_pr = h_qs = 0,
+// ROUND_ANTI h_ps = h_qr = 0.  The first product then has one term per entry instead of two, 8 instructions instead of 16,
+// and the same values (x + t * 0 = x) up to the sign of a zero.
+enum RoundZeros : int { ROUND_FULL = 0, ROUND_DIAG = 1, ROUND_ANTI = 2 };
+
+template <int ZEROS>
+SYMPA_HD void jacobi_round(Herm<4>& h, const int p, const int q, const int r, const int s) {
+    double ca, ar, ai, ua, cb, br, bi, ub;
+    jacobi_angle<4>(h, p, q, ca, ar, ai, ua);      // neither rotation changes what the other one's parameters read
+    jacobi_angle<4>(h, r, s, cb, br, bi, ub);
+    h.d[p] -= ua;
+    h.d[q] += ua;
+    h.d[r] -= ub;
+    h.d[s] += ub;
+    h.re[p][q] = 0.0;
+    h.im[p][q] = 0.0;
+    h.re[r][s] = 0.0;
+    h.im[r][s] = 0.0;
+    const double cc = ca * cb;
+    const int row[2] = {p, q}, col[2] = {r, s};
+    double mr[2][2], mi[2][2];
+SYMPA_UNROLL
+    for (int i = 0; i < 2; ++i) {
+SYMPA_UNROLL
+        for (int j = 0; j < 2; ++j) herm_get<4>(h, row[i], col[j], mr[i][j], mi[i][j]);
+    }
+    // P = T_A^H M:  P_p. = M_p. - tau_A M_q. ,  P_q. = conj(tau_A) M_p. + M_q.
+    double pr[2][2], pi[2][2];
+SYMPA_UNROLL
+    for (int j = 0; j < 2; ++j) {
+        if ((ZEROS == ROUND_DIAG && j == 0) || (ZEROS == ROUND_ANTI && j == 1)) {          // M_pj = 0
+            pr[0][j] = d_fma(ai, mi[1][j], -ar * mr[1][j]);
+            pi[0][j] = d_fma(-ai, mr[1][j], -ar * mi[1][j]);
+            pr[1][j] = mr[1][j];
+            pi[1][j] = mi[1][j];
+        } else if ((ZEROS == ROUND_DIAG && j == 1) || (ZEROS == ROUND_ANTI && j == 0)) {   // M_qj = 0
+            pr[0][j] = mr[0][j];
+            pi[0][j] = mi[0][j];
+            pr[1][j] = d_fma(ai, mi[0][j], ar * mr[0][j]);
+            pi[1][j] = d_fma(-ai, mr[0][j], ar * mi[0][j]);
+        } else {
+            pr[0][j] = d_fma(ai, mi[1][j], d_fma(-ar, mr[1][j], mr[0][j]));
+            pi[0][j] = d_fma(-ai, mr[1][j], d_fma(-ar, mi[1][j], mi[0][j]));
+            pr[1][j] = d_fma(ai, mi[0][j], d_fma(ar, mr[0][j], mr[1][j]));
+            pi[1][j] = d_fma(-ai, mr[0][j], d_fma(ar, mi[0][j], mi[1][j]));
+        }
+    }
+    // Q = P T_B:  Q_.r = P_.r - conj(tau_B) P_.s ,  Q_.s = tau_B P_.r + P_.s ;  M <- (c_A c_B) Q
+SYMPA_UNROLL
+    for (int i = 0; i < 2; ++i) {
+        const double q0r = d_fma(-bi, pi[i][1], d_fma(-br, pr[i][1], pr[i][0]));
+        const double q0i = d_fma(bi, pr[i][1], d_fma(-br, pi[i][1], pi[i][0]));
+        const double q1r = d_fma(-bi, pi[i][0], d_fma(br, pr[i][0], pr[i][1]));
+        const double q1i = d_fma(bi, pr[i][0], d_fma(br, pi[i][0], pi[i][1]));
+        herm_set<4>(h, row[i], col[0], cc * q0r, cc * q0i);
+        herm_set<4>(h, row[i], col[1], cc * q1r, cc * q1i);
+    }
+}
+
+// after_sweep: the matrix comes out of a sweep of this function (n = 4: h_03 = h_12 = 0 exactly, the first round may rely on it)
+template <int N>
+SYMPA_HD void jacobi_sweep(Herm<N>& h, const bool after_sweep = false) {
+    if constexpr (N == 4) {   // round-robin: 3 rounds of 2 disjoint rotations
+        if (after_sweep) jacobi_round<ROUND_ANTI>(h, 0, 1, 2, 3);
+        else jacobi_round<ROUND_FULL>(h, 0, 1, 2, 3);
+        jacobi_round<ROUND_DIAG>(h, 0, 2, 1, 3);
+        jacobi_round<ROUND_ANTI>(h, 0, 3, 1, 2);
     } else {        // cyclic by rows
 SYMPA_UNROLL
         for (int p = 0; p < N - 1; ++p) {
@@ -460,27 +561,57 @@ SYMPA_UNROLL
 // and graded spectra (lambda_max / lambda_min ~ 1e10 near the clamp) need the small eigenvalues to RELATIVE
 // accuracy for fone / fmin: a looser pair (t^2 <= 1e-4, off <= 1e-8) measured 8e-8 on the bounded n = 8 golden
 // vectors, so the certificate stays at t^2 <= 1e-8, off <= 1e-12 (dropped terms <= 6e-13 ||H||).
+// The certificate below has |h_pq|^2 of every pivot in hand when it lets the iteration end: it hands them over (a2[], pivots in
+// row order) instead of the finishing sweep forming them again.  The differences delta are NOT handed over: the finishing
+// sweep reads each one from the diagonal as the pivots before it have left it.
+// The shift itself: with t = a / |delta|,  r = |delta| sqrt(1 + 4 t^2)  and
+//   t |beta| = 2 a^2 / (|delta| + r) = a^2 / (|delta| (1 + t^2 - t^4 + ...)) = a^2 delta / (delta^2 + a^2) * (1 + O(t^4)),
+// one reciprocal and no square root; the O(t^4) is the order the finishing sweep drops anyway (t^2 <= 1e-3 under the certificate;
+// the form with r and 1 / c^2 = 2 - c^2 it replaces dropped the same order).  A pivot the certificate passed as negligible
+// (a^2 <= 1e-24 ||diag||^2) may have any t: its shift is at most a <= 1e-12 ||diag|| in either form.  |delta| + 1e-150 keeps the
+// denominator positive when a = delta = 0.
 template <int N>
-SYMPA_HD void jacobi_diag_update(Herm<N>& h, const int p, const int q) {
-    const double br = h.re[p][q], bi = h.im[p][q];
-    const double a2 = d_fma(br, br, bi * bi);
+SYMPA_HD void jacobi_diag_update(Herm<N>& h, const int p, const int q, const double a2) {
     const double delta = h.d[q] - h.d[p];
     const double ad = fabs(delta) + 1e-150;
-    const double qr = d_rsqrt(d_fma(ad, ad, 4.0 * a2));
-    const double c2 = d_fma(0.5 * ad, qr, 0.5);
-    // t |beta| = a^2 / (r c^2);  1 / c^2 = 2 - c^2 + O(t^4)
-    const double ua2 = (copysign(qr, delta) * a2) * (2.0 - c2);
+    const double ua2 = (a2 * delta) * d_rcp(d_fma(ad, ad, a2));
     h.d[p] -= ua2;
     h.d[q] += ua2;
 }
 
+template <int N> constexpr int herm_pivots() { return N > 1 ? N * (N - 1) / 2 : 1; }   // (an array length: never 0)
+
+// |h_pq|^2 of every pivot, row order
 template <int N>
-SYMPA_HD void jacobi_final_sweep(Herm<N>& h) {
+SYMPA_HD void herm_pivot_a2(const Herm<N>& h, double (&a2)[herm_pivots<N>()]) {
+    int k = 0;
 SYMPA_UNROLL
     for (int p = 0; p < N - 1; ++p) {
 SYMPA_UNROLL
-        for (int q = p + 1; q < N; ++q) jacobi_diag_update<N>(h, p, q);
+        for (int q = p + 1; q < N; ++q, ++k) a2[k] = d_fma(h.re[p][q], h.re[p][q], h.im[p][q] * h.im[p][q]);
     }
+}
+
+// AFTER_SWEEP: the matrix comes out of jacobi_sweep.  For n = 4 its last round has left h_03 = h_12 = 0 exactly: the shift of
+// those two pivots is a zero, they are passed over.
+template <int N, bool AFTER_SWEEP>
+SYMPA_HD void jacobi_final_sweep(Herm<N>& h, const double (&a2)[herm_pivots<N>()]) {
+    int k = 0;
+SYMPA_UNROLL
+    for (int p = 0; p < N - 1; ++p) {
+SYMPA_UNROLL
+        for (int q = p + 1; q < N; ++q, ++k) {
+            if (AFTER_SWEEP && N == 4 && p + q == 3) continue;
+            jacobi_diag_update<N>(h, p, q, a2[k]);
+        }
+    }
+}
+
+template <int N>
+SYMPA_HD void jacobi_final_sweep(Herm<N>& h) {
+    double a2[herm_pivots<N>()];
+    herm_pivot_a2<N>(h, a2);
+    jacobi_final_sweep<N, false>(h, a2);
 }
 
 // Certificate for the finishing sweep (thresholds above): every pivot has t^2 = |h_pq|^2 / delta^2 small, or is
@@ -491,23 +622,24 @@ template <int N> constexpr double finish_off2() { return N <= 4 ? 1e-4 : 1e-12; 
 constexpr double FINISH_NEGLIGIBLE2 = 1e-24;
 
 template <int N>
-SYMPA_HD bool jacobi_can_finish(const Herm<N>& h) {
+SYMPA_HD bool jacobi_can_finish(const Herm<N>& h, double (&a2)[herm_pivots<N>()]) {
     double diag2 = 0.0;
 SYMPA_UNROLL
     for (int j = 0; j < N; ++j) diag2 = d_fma(h.d[j], h.d[j], diag2);
     const double floor2 = FINISH_NEGLIGIBLE2 * diag2;
+    herm_pivot_a2<N>(h, a2);
     double off2 = 0.0;
     bool ok = true;
+    int k = 0;
 SYMPA_UNROLL
     for (int p = 0; p < N - 1; ++p) {
 SYMPA_UNROLL
-        for (int q = p + 1; q < N; ++q) {
-            const double a2 = d_fma(h.re[p][q], h.re[p][q], h.im[p][q] * h.im[p][q]);
+        for (int q = p + 1; q < N; ++q, ++k) {
             const double delta = h.d[q] - h.d[p];
-            off2 += a2;
+            off2 += a2[k];
             // written so that a NaN (non-finite input) counts as "finished": no extra sweeps are spent on it, the
             // eigenvalues are tested for finiteness afterwards (pair_distance_mats)
-            ok = ok && !(a2 > fmax(finish_t2<N>() * delta * delta, floor2));
+            ok = ok && !(a2[k] > fmax(finish_t2<N>() * delta * delta, floor2));
         }
     }
     return ok && !(off2 > finish_off2<N>() * diag2);
@@ -523,15 +655,18 @@ template <int N>
 SYMPA_HD bool herm_eigenvalues_jacobi(Herm<N>& h) {
     if (N == 1) return true;
 SYMPA_UNROLL
-    for (int sweep = 0; sweep < jacobi_blind_sweeps<N>(); ++sweep) jacobi_sweep<N>(h);
+    for (int sweep = 0; sweep < jacobi_blind_sweeps<N>(); ++sweep) jacobi_sweep<N>(h, sweep > 0);
     if (N == 2) return true;    // a single rotation diagonalises a 2 x 2 matrix exactly
     bool conv = false;
-    for (int sweep = jacobi_blind_sweeps<N>(); sweep < JACOBI_MAX_SWEEPS; ++sweep) {
-        conv = jacobi_can_finish<N>(h);
+    double a2[herm_pivots<N>()];
+    int sweep = jacobi_blind_sweeps<N>();
+    for (; sweep < JACOBI_MAX_SWEEPS; ++sweep) {
+        conv = jacobi_can_finish<N>(h, a2);
         if (wave_all(conv)) break;
-        jacobi_sweep<N>(h);
+        jacobi_sweep<N>(h, true);
     }
-    jacobi_final_sweep<N>(h);
+    if (sweep == JACOBI_MAX_SWEEPS) herm_pivot_a2<N>(h, a2);   // the cap: a sweep has run since the certificate looked
+    jacobi_final_sweep<N, true>(h, a2);
     return conv;
 }
 
@@ -543,10 +678,6 @@ SYMPA_UNROLL
 // Everything stays in registers: loops are static, the per-lane active block [l, m] of the QL iteration is
 // handled by predication, the iteration ends when every lane of the wave has deflated all off-diagonals.
 // ---------------------------------------------------------------------------------------------
-template <int N>
-SYMPA_HD void herm_get(const Herm<N>& h, int i, int j, double& re, double& im) {   // element (i, j), i != j
-    if (i < j) { re = h.re[i][j]; im = h.im[i][j]; } else { re = h.re[j][i]; im = -h.im[j][i]; }
-}
 
 template <int N>
 SYMPA_HD void herm_tridiagonalize(Herm<N>& h, double (&a)[N], double (&b2)[N]) {
