@@ -520,6 +520,59 @@ int sympa_spd_projx(const double* x, int64_t b, int n, double* out, int32_t* pro
 int sympa_spd_rsgd_step(double* table, const double* grad, int64_t num_rows, int n, double lr, double weight_decay,
                         const double* total_sqnorm, double max_norm, int32_t* status, void* stream);
 
+/* ---- Vector models (manifolds "euclidean", "poincare", "lorentz", "sphere", "prod-hysph", "prod-hyhy", "prod-hyeu",
+ * "prod-sphsph": geoopt constructors behind ManifoldFactory, sympa/embeddings.py:130-158, and VectorEmbeddings,
+ * sympa/embeddings.py:82-90).  geoopt is not in the reference tree: PARITY UNPINNED like the spd entries; the definitions are
+ * the project's own and the kernels are pinned to 50-digit evaluations of them
+ * (tests/golden/exact_vector_*.npz).  A point is a row of `dims` doubles (1 <= dims <= 1024, else SYMPA_ERR_UNSUPPORTED_DIMS),
+ * split into one or two factors; products need even dims, sphere / lorentz factors at least two coordinates
+ * (SYMPA_ERR_BAD_ARG).  Per factor, J = diag(-1, 1, ..., 1) for lorentz and I otherwise,
+ *     dd = sum J_i (x_i - y_i)^2,  xx = sum x_i^2,  yy = sum y_i^2,
+ *     E: d = sqrt(dd)    P: d = 2 asinh sqrt(dd / ((1 - xx)(1 - yy)))    L: d = 2 asinh sqrt(max(dd, 0) / 4)
+ *     S: d = 2 asin sqrt(min(dd / 4, 1)),   a product: sqrt(d_1^2 + d_2^2).
+ * A Poincare point with xx >= 1 gives NaN and SYMPA_ST_NOT_PD, a non-finite value NaN and SYMPA_ST_NONFINITE.  G lanes per
+ * pair / row, G = 1..64 from dims (csrc/vector_models.hip); a pair's value is the same bits in all three forward entries.
+ * `flags` is reserved (0). */
+#define SYMPA_VECTOR_EUCLIDEAN 0
+#define SYMPA_VECTOR_POINCARE 1
+#define SYMPA_VECTOR_LORENTZ 2
+#define SYMPA_VECTOR_SPHERE 3
+#define SYMPA_VECTOR_PROD_HYSPH 4
+#define SYMPA_VECTOR_PROD_HYHY 5
+#define SYMPA_VECTOR_PROD_HYEU 6
+#define SYMPA_VECTOR_PROD_SPHSPH 7
+/* manifold.dist(x, y) on rows i of x and y [b, dims] (geoopt Manifold.dist behind sympa/model.py:32-38) */
+int sympa_vector_dist_fwd(const double* x, const double* y, int64_t b, int dims, int model, double* out, int32_t* status,
+                          int flags, void* stream);
+/* Model.forward (sympa/model.py:16-41) over a [num_rows, dims] table: gather, distance, scale */
+int sympa_vector_model_forward(const double* table, int64_t num_rows, int dims, const int64_t* src, int64_t src_stride,
+                               const int64_t* dst, int64_t dst_stride, int64_t b, int model, const double* scale,
+                               double scale_coef, double* out, int32_t* status, int flags, void* stream);
+/* Runner.build_distance_matrix (sympa/runner.py:142-154): rows [row_begin, row_begin + row_count) of the N x N matrix into
+ * out [row_count, num_rows]; the same pair kernel with i = row_begin + p / N, j = p % N computed in the kernel, no pair list.
+ * The diagonal is exactly 0 and (i, j) is bit-equal to (j, i). */
+int sympa_vector_all_pairs_dist(const double* table, int64_t num_rows, int dims, int64_t row_begin, int64_t row_count, int model,
+                                const double* scale, double scale_coef, double* out, int32_t* status, int flags, void* stream);
+/* Backward of the two entries above (sympa/model.py:16-41 under runner.py:105), shaped like sympa_spd_backward_rows: pair
+ * i = (x[src[i]], y[dst[i]]) (src = dst = NULL: rows i); grad_out [b] or graph_dist [b] (AverageDistortionLoss of
+ * sympa/losses.py:10-19 fused: loss[0] += loss_scale * sum |(out / graph_dist)^2 - 1|); grad_x_rows / grad_y_rows [b, dims]
+ * are WRITTEN (accumulate them with sympa_scatter_add_flat_rows or sympa_segment_sum_rows, row_doubles = dims); grad_scale [1]
+ * accumulated, out [b] optional.  A factor with q == 0 (src == dst among them) contributes a zero gradient, never NaN. */
+int sympa_vector_backward_rows(const double* x, const double* y, int64_t num_rows, int dims, int model, const int64_t* src,
+                               int64_t src_stride, const int64_t* dst, int64_t dst_stride, int64_t b, const double* scale,
+                               double scale_coef, const double* grad_out, const double* graph_dist, double loss_scale,
+                               double* loss, double* grad_x_rows, double* grad_y_rows, double* grad_scale, double* out,
+                               int32_t* status, int flags, void* stream);
+/* geoopt's egrad2rgrad, projx (projected_count += rows whose Poincare factor was rescaled to norm 1 - 1e-5) and one
+ * geoopt.optim.RiemannianSGD step (momentum 0; train.py:66-68) over the table in place, per factor
+ *     g <- grad + weight_decay x,   x <- retr(x, -lr egrad2rgrad(x, g)),
+ * with the gradient clip of runner.py:115 folded in when total_sqnorm (device, squared total norm) is given. */
+int sympa_vector_egrad2rgrad(const double* x, const double* u, int64_t b, int dims, int model, double* out, void* stream);
+int sympa_vector_projx(const double* x, int64_t b, int dims, int model, double* out, int32_t* projected_count, int32_t* status,
+                       void* stream);
+int sympa_vector_rsgd_step(double* table, const double* grad, int64_t num_rows, int dims, int model, double lr, double weight_decay,
+                           const double* total_sqnorm, double max_norm, int32_t* projected_count, int32_t* status, void* stream);
+
 /* Per-row average precision of a block of rows of the all-pairs distance matrix: the ranking half of
  * MeanAveragePrecisionMetric.calculate_metric (sympa/metrics.py:39-63) over the matrix Runner.calculate_mAP builds
  * (sympa/runner.py:137-154), without sorting the rows (csrc/map_rank.hip).

@@ -65,6 +65,13 @@ SYMBOLS = (
     "sympa_spd_egrad2rgrad",
     "sympa_spd_projx",
     "sympa_spd_rsgd_step",
+    "sympa_vector_dist_fwd",
+    "sympa_vector_model_forward",
+    "sympa_vector_all_pairs_dist",
+    "sympa_vector_backward_rows",
+    "sympa_vector_egrad2rgrad",
+    "sympa_vector_projx",
+    "sympa_vector_rsgd_step",
     "sympa_map_workspace_bytes",
     "sympa_map_rows",
     "sympa_graph_hops_workspace_bytes",
@@ -283,6 +290,27 @@ def load():
     lib.sympa_spd_rsgd_step.argtypes = [_c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
                                         ctypes.c_double, _c_double_p, ctypes.c_double, _c_i32_p, ctypes.c_void_p]
     C = ctypes
+    lib.sympa_vector_dist_fwd.restype = C.c_int
+    lib.sympa_vector_dist_fwd.argtypes = [_c_double_p, _c_double_p, C.c_int64, C.c_int, C.c_int, _c_double_p, _c_i32_p, C.c_int,
+                                          C.c_void_p]
+    lib.sympa_vector_model_forward.restype = C.c_int
+    lib.sympa_vector_model_forward.argtypes = [_c_double_p, C.c_int64, C.c_int, _c_i64_p, C.c_int64, _c_i64_p, C.c_int64, C.c_int64,
+                                               C.c_int, _c_double_p, C.c_double, _c_double_p, _c_i32_p, C.c_int, C.c_void_p]
+    lib.sympa_vector_all_pairs_dist.restype = C.c_int
+    lib.sympa_vector_all_pairs_dist.argtypes = [_c_double_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, _c_double_p,
+                                                C.c_double, _c_double_p, _c_i32_p, C.c_int, C.c_void_p]
+    lib.sympa_vector_backward_rows.restype = C.c_int
+    lib.sympa_vector_backward_rows.argtypes = [
+        _c_double_p, _c_double_p, C.c_int64, C.c_int, C.c_int, _c_i64_p, C.c_int64, _c_i64_p, C.c_int64, C.c_int64, _c_double_p,
+        C.c_double, _c_double_p, _c_double_p, C.c_double, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+        _c_i32_p, C.c_int, C.c_void_p]
+    lib.sympa_vector_egrad2rgrad.restype = C.c_int
+    lib.sympa_vector_egrad2rgrad.argtypes = [_c_double_p, _c_double_p, C.c_int64, C.c_int, C.c_int, _c_double_p, C.c_void_p]
+    lib.sympa_vector_projx.restype = C.c_int
+    lib.sympa_vector_projx.argtypes = [_c_double_p, C.c_int64, C.c_int, C.c_int, _c_double_p, _c_i32_p, _c_i32_p, C.c_void_p]
+    lib.sympa_vector_rsgd_step.restype = C.c_int
+    lib.sympa_vector_rsgd_step.argtypes = [_c_double_p, _c_double_p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double,
+                                           _c_double_p, C.c_double, _c_i32_p, _c_i32_p, C.c_void_p]
     lib.sympa_table_pack_bytes.restype = C.c_int64
     lib.sympa_table_pack_bytes.argtypes = [C.c_int64, C.c_int, C.c_int]
     lib.sympa_table_pack.restype = C.c_int

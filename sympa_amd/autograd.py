@@ -119,3 +119,56 @@ def spd_model_forward(table, triplets, scale=None, scale_coef=1.0):
     if _needs_grad(table, scale):
         return _SpdModelForwardFn.apply(table, triplets, scale, scale_coef)
     return ops.spd_model_forward(table, triplets, scale, scale_coef)
+
+
+class _VectorDistFn(torch.autograd.Function):
+    """dist(x, y) of a vector model on [b, dims] rows with the analytic backward (sympa_vector_backward_rows)."""
+
+    @staticmethod
+    def forward(ctx, x, y, model):
+        ctx.save_for_backward(x, y)
+        ctx.model = model
+        return ops.vector_dist_forward(x, y, model)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, y = ctx.saved_tensors
+        rows, _ = ops.vector_backward_rows(x, y, ctx.model, grad_out=grad_out)
+        b = x.shape[0]
+        return rows[:b], rows[b:], None
+
+
+def vector_dist(x, y, model):
+    if _needs_grad(x, y):
+        return _VectorDistFn.apply(x, y, model)
+    return ops.vector_dist_forward(x, y, model)
+
+
+class _VectorModelForwardFn(torch.autograd.Function):
+    """Model.forward for a vector model: dense [N, dims] table gradient = per-pair rows + the scatter-add kernel."""
+
+    @staticmethod
+    def forward(ctx, table, triplets, model, scale, scale_coef):
+        ctx.save_for_backward(table, triplets, scale if scale is not None else torch.empty(0, device=table.device))
+        ctx.cfg = (model, scale_coef, scale is not None)
+        return ops.vector_model_forward(table, triplets, model, scale, scale_coef)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        table, triplets, scale = ctx.saved_tensors
+        model, scale_coef, has_scale = ctx.cfg
+        scale = scale if has_scale else None
+        gs = torch.zeros(1, dtype=torch.float64, device=table.device) if has_scale else None
+        rows, _ = ops.vector_backward_rows(table, table, model, triplets, grad_out=grad_out, scale=scale, scale_coef=scale_coef,
+                                           grad_scale=gs)
+        gt = torch.zeros_like(table, memory_format=torch.contiguous_format)
+        idx = torch.cat((triplets[:, 0], triplets[:, 1])).contiguous()
+        ops.scatter_add_flat_rows_(gt, rows, idx)
+        return (gt if ctx.needs_input_grad[0] else None, None, None,
+                gs.reshape(scale.shape) if (has_scale and ctx.needs_input_grad[3]) else None, None)
+
+
+def vector_model_forward(table, triplets, model, scale=None, scale_coef=1.0):
+    if _needs_grad(table, scale):
+        return _VectorModelForwardFn.apply(table, triplets, model, scale, scale_coef)
+    return ops.vector_model_forward(table, triplets, model, scale, scale_coef)

@@ -1,8 +1,9 @@
-"""Embedding table + factories for the matrix models (reference sympa/embeddings.py).
+"""Embedding tables + factories (reference sympa/embeddings.py).
 
-Only the Siegel models are in scope: `upper`, `bounded`.  The vector models and
-`spd` live in geoopt, not in the reference, and are not part of this hot path; asking for them
-raises with that explanation."""
+The matrix models `upper`, `bounded`, `dual` and `spd` keep a [N, 2, n, n] / [N, n, n] table (MatrixEmbeddings); the eight
+vector models `euclidean`, `poincare`, `lorentz`, `sphere`, `prod-hysph`, `prod-hyhy`, `prod-hyeu`, `prod-sphsph` keep a
+[N, dims] table (VectorEmbeddings, sympa_amd/manifolds/vector.py).  `spd` and the vector models are geoopt classes in the
+reference, whose arithmetic is not in the reference tree: their definitions are restated here (DESIGN.md sections 12, 19)."""
 import abc
 
 import torch
@@ -12,6 +13,7 @@ from sympa_amd import config
 from sympa_amd.manifolds import BoundedDomainManifold, CompactDualManifold, SymmetricPositiveDefinite, UpperHalfManifold
 from sympa_amd.manifolds.base import ManifoldParameter
 from sympa_amd.manifolds.metrics import MetricType
+from sympa_amd.manifolds.vector import get_vector_manifold
 
 
 class Embeddings(nn.Module, abc.ABC):
@@ -81,6 +83,29 @@ class MatrixEmbeddings(Embeddings):
         return points.reshape(len(points), -1).norm(dim=-1)
 
 
+class VectorEmbeddings(Embeddings):
+    """Table of vectors: num_embeddings x dims (embeddings.py:82-90): uniform(-INIT_EPS, INIT_EPS), proj_embeds(), norm()."""
+
+    def __init__(self, num_embeddings, dims, manifold):
+        _embeds = torch.empty(num_embeddings, dims, dtype=config.DEFAULT_DTYPE).uniform_(-config.INIT_EPS, config.INIT_EPS)
+        super().__init__(num_embeddings, dims, manifold, _embeds)
+        self.proj_embeds()
+
+    def check_all_points(self):
+        """The verdict of embeddings.py:41-47 from batched ops with ONE host sync (the index of the first bad row, or -1)."""
+        pts = self.embeds.data
+        bad = self.manifold.bad_rows(pts)
+        first = int(torch.where(bad.any(), bad.to(torch.int64).argmax(), torch.full((), -1, dtype=torch.int64, device=pts.device)))
+        if first < 0:
+            return True, None, None
+        point = pts[first]
+        ok, reason = self.manifold.check_point_on_manifold(point, explain=True)
+        return (True, None, None) if ok else (False, point, reason)
+
+    def norm(self):
+        return self.embeds.data.norm(dim=-1)
+
+
 class EmbeddingsFactory:
     @classmethod
     def get_embeddings(cls, name: str, num_points: int, dims: int, manifold):
@@ -90,14 +115,17 @@ class EmbeddingsFactory:
     def _get_table(cls, model_name: str):
         if model_name in ManifoldFactory.sympa_manifolds or model_name == "spd":
             return MatrixEmbeddings
+        if model_name in ManifoldFactory.vector_manifolds:
+            return VectorEmbeddings
         raise ValueError(f"Unrecognized embedding model for the Siegel hot path: {model_name}")
 
 
 class ManifoldFactory:
     sympa_manifolds = {"upper": UpperHalfManifold, "bounded": BoundedDomainManifold,
                        "dual": CompactDualManifold}                                   # embeddings.py:145-149
-    out_of_scope = {"euclidean", "poincare", "lorentz", "sphere",
-                    "prod-hysph", "prod-hyhy", "prod-hyeu", "prod-sphsph"}
+    vector_manifolds = ("euclidean", "poincare", "lorentz", "sphere",
+                        "prod-hysph", "prod-hyhy", "prod-hyeu", "prod-sphsph")          # embeddings.py:130-158
+    out_of_scope = set()       # every manifold name of the reference is built
 
     @classmethod
     def get_manifold(cls, manifold_name, metric_name, dims):
@@ -105,6 +133,8 @@ class ManifoldFactory:
             raise NotImplementedError(
                 f"manifold '{manifold_name}' is outside the MI355X hot path (SURVEY section 2: its "
                 "arithmetic lives in geoopt / xitorch, not in the reference)")
+        if manifold_name in cls.vector_manifolds:
+            return get_vector_manifold(manifold_name, dims)
         if manifold_name == "spd":      # embeddings.py:142
             return SymmetricPositiveDefinite()
         manifold = cls.sympa_manifolds[manifold_name]

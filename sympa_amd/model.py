@@ -41,6 +41,25 @@ class _SpdBatches:
             ops.spd_model_forward(m.embeddings.embeds.data, t, m.scale.data, m.scale_coef, out=o)
 
 
+class _VectorBatches:
+    """forward_batches for the vector models: one launch per batch (the pair kernel is memory bound: no multi-batch kernel)."""
+
+    def __init__(self, model, batches, outs):
+        self.model, self.batches, self.outs = model, batches, outs
+
+    def set_streams(self, streams):
+        pass
+
+    def run(self):
+        m = self.model
+        for t, o in zip(self.batches, self.outs):
+            ops.vector_model_forward(m.embeddings.embeds.data, t, m.manifold.model_name, m.scale.data, m.scale_coef, out=o)
+
+
+def _is_vector(man):
+    return getattr(man, "model_name", None) in ops.VECTOR_MODEL_IDS
+
+
 class Model(nn.Module):
     def __init__(self, args):
         super().__init__()
@@ -61,7 +80,7 @@ class Model(nn.Module):
         distortion read the live attributes."""
         man = self.manifold
         emb = self.embeddings
-        spd = man.model_name == "spd"
+        spd = man.model_name == "spd" or _is_vector(man)           # the models without a metric module
         metric = None if spd else man.metric
         wsum = (not spd) and metric.kind is MetricType.WEIGHTED_SUM
         c = (emb.embeds, self.scale, metric.weights if wsum else None, man.model_name,
@@ -90,7 +109,9 @@ class Model(nn.Module):
         if c is None or not self._forward_cache_valid(c):
             c = self._forward_cache()
         table, scale, weights, model_name, metric_name = c[:5]
-        if model_name == "spd":
+        if model_name == "spd" or (metric_name is None and model_name in ops.VECTOR_MODEL_IDS):
+            if model_name != "spd":
+                return sa.vector_model_forward(table, input_triplet, model_name, scale, self.scale_coef)
             if not (torch.is_grad_enabled() and (table.requires_grad or scale.requires_grad)) and \
                     input_triplet.shape[0] >= PACKED_MIN_PAIRS:
                 pk = self.packed_table()            # no autograd graph to build: the packed table once its version is seen twice
@@ -136,7 +157,7 @@ class Model(nn.Module):
     def _metric_key(self):
         """What a cached plan bakes in of the metric: its kind and the address of the wsum weights."""
         man = self.manifold
-        if man.model_name == "spd":
+        if man.model_name == "spd" or _is_vector(man):
             return None
         k = man.metric.kind
         return (k.value, man.metric.weights.data_ptr() if k is MetricType.WEIGHTED_SUM else 0)
@@ -160,6 +181,8 @@ class Model(nn.Module):
         outs = list(outs)
         if man.model_name == "spd":
             return _SpdBatches(self, batches, outs)
+        if _is_vector(man):
+            return _VectorBatches(self, batches, outs)
         weights = man.metric.weights if man.metric.kind is MetricType.WEIGHTED_SUM else None
         pk = self.packed_table()
         if pk is not None and sum(int(t.shape[0]) for t in batches) >= PACKED_MIN_PAIRS:
@@ -234,6 +257,24 @@ class Model(nn.Module):
         dev = table.device
         if table.grad is None:
             table.grad = torch.zeros_like(table.data)
+        if _is_vector(man):
+            # two launches: per-pair gradient rows (backward + loss fused), then the coalesced scatter-add
+            gs = self._scale_grad()
+            loss = torch.zeros(1, dtype=torch.float64, device=dev) if loss_out is None else (loss_out.zero_() if zero_loss_out else loss_out)
+            b = input_triplet.shape[0]
+            dims = table.shape[-1]
+            ws = getattr(self, "_vector_rows", None)
+            if ws is None or ws.shape[0] < 2 * b or ws.device != dev:
+                ws = torch.empty(2 * b, dims, dtype=torch.float64, device=dev)
+                self._vector_rows = ws
+            if not table.grad.is_contiguous():
+                raise ValueError("the table gradient must be contiguous")
+            ops.vector_backward_rows(table.data, table.data, man.model_name, input_triplet, graph_dist=graph_distances,
+                                     scale=self.scale.data, scale_coef=self.scale_coef, loss_scale=loss_scale, loss=loss,
+                                     grad_scale=gs, rows=ws)
+            idx = torch.cat((input_triplet[:, 0], input_triplet[:, 1])).contiguous()
+            ops.scatter_add_flat_rows_(table.grad, ws[:2 * b], idx)
+            return loss
         if man.model_name == "spd":
             # n <= 2: two launches, per-pair gradient rows (backward + loss fused), then the coalesced scatter-add
             gs = None
@@ -276,6 +317,14 @@ class Model(nn.Module):
                                 gs, self.scale_coef, loss_scale)
         return loss
 
+    def _scale_grad(self):
+        """scale.grad (created on first use) when the scale is trained, else None."""
+        if not self.scale.requires_grad:
+            return None
+        if self.scale.grad is None:
+            self.scale.grad = torch.zeros_like(self.scale.data)
+        return self.scale.grad
+
     def fused_loss_backward_rows(self, input_triplet, graph_distances, grad_rows, loss_scale=1.0):
         """fused_loss_backward with the table gradient left as per-pair rows in `grad_rows` [2b, 2, n, n] (written;
         rows [0, b) belong to the src ids, [b, 2b) to the dst ids) for the touched-row gradient exchange of
@@ -283,6 +332,13 @@ class Model(nn.Module):
         from sympa_amd import ops
         man = self.manifold
         table = self.embeddings.embeds
+        if _is_vector(man):
+            # grad_rows [2b, dims]: written; accumulate with ops.scatter_add_flat_rows_ or, deterministically, ops.segment_sum_rows_
+            loss = torch.zeros(1, dtype=torch.float64, device=table.device)
+            ops.vector_backward_rows(table.data, table.data, man.model_name, input_triplet, graph_dist=graph_distances,
+                                     scale=self.scale.data, scale_coef=self.scale_coef, loss_scale=loss_scale, loss=loss,
+                                     grad_scale=self._scale_grad(), rows=grad_rows.view(-1, table.shape[-1]))
+            return loss
         if man.model_name == "spd":
             gs = None
             if self.scale.requires_grad:
@@ -317,6 +373,9 @@ class Model(nn.Module):
         forward calls, as one launch (or one launch per row block).  Diagonal exactly 0."""
         from sympa_amd import ops
         man = self.manifold
+        if _is_vector(man):
+            # the pair kernel with (i, j) computed from the pair number: no pair list; diagonal exactly 0, exactly symmetric
+            return ops.vector_all_pairs_dist(self.embeddings.embeds, man.model_name, self.scale, self.scale_coef, row_begin, row_count)
         if man.model_name == "spd":
             # the same pairs (i, j) the reference's loop feeds to forward(), through the spd kernel
             emb = self.embeddings.embeds
@@ -356,6 +415,7 @@ class Model(nn.Module):
         metric = triples_or_metric if isinstance(triples_or_metric, sm.MeanAveragePrecisionMetric) else \
             sm.MeanAveragePrecisionMetric(triples_or_metric)
         nbrs = metric.csr(N, dev)
+        vec = _is_vector(man)
         spd = man.model_name == "spd"
         row_bytes = (8 + 16 + 16) * N if spd else 8 * N       # spd: output + [N, 2] pair list + the arange repeats behind it
         R = max(1, int(max_block_bytes) // row_bytes)
@@ -363,7 +423,9 @@ class Model(nn.Module):
         R = min(R, max(count, 1))
         ap = torch.zeros(N, dtype=torch.float64, device=dev)
         float32 = dtype == torch.float32
-        if not spd:
+        if vec:
+            buf = torch.empty(R, N, dtype=torch.float64, device=dev) if count > 0 else None
+        elif not spd:
             weights = man.metric.weights if man.metric.kind is MetricType.WEIGHTED_SUM else None
             n = table.shape[-1]
             need = ops._lib.load().sympa_all_pairs_workspace_bytes(N, n, ops.MODEL_IDS[man.model_name])
@@ -372,7 +434,9 @@ class Model(nn.Module):
         with torch.no_grad():
             for b in range(begin, begin + count, R):
                 r = min(R, begin + count - b)
-                if spd:
+                if vec:
+                    rows = ops.vector_all_pairs_dist(table, man.model_name, self.scale.detach(), self.scale_coef, b, r, out=buf[:r])
+                elif spd:
                     rows = self.distance_matrix(b, r)
                 else:
                     rows = ops.all_pairs_dist(table, man.model_name, man.metric.kind.value, weights, self.scale.detach(),
@@ -409,6 +473,7 @@ class Model(nn.Module):
             raise ValueError(f"the graph has {gd.num_nodes} nodes but the table {N} rows")
         if gd.device != dev:
             raise ValueError(f"the graph distances live on {gd.device}, the table on {dev}")
+        vec = _is_vector(man)
         spd = man.model_name == "spd"
         # a WeightedGraphDistances differs in the dtype of the graph rows and in the kernel that reduces them; the rest is shared
         weighted = isinstance(gd, WeightedGraphDistances)
@@ -422,7 +487,9 @@ class Model(nn.Module):
         pairs = torch.zeros(N, dtype=torch.int64, device=dev)
         if count > 0:
             hbuf = torch.empty(R, N, dtype=torch.float64 if weighted else torch.int32, device=dev)
-            if not spd:
+            if vec:
+                dbuf = torch.empty(R, N, dtype=torch.float64, device=dev)
+            elif not spd:
                 weights = man.metric.weights if man.metric.kind is MetricType.WEIGHTED_SUM else None
                 need = ops._lib.load().sympa_all_pairs_workspace_bytes(N, table.shape[-1], ops.MODEL_IDS[man.model_name])
                 ws = torch.empty(need // 8, dtype=torch.float64, device=dev) if need > 0 else None
@@ -430,7 +497,9 @@ class Model(nn.Module):
         with torch.no_grad():
             for b in range(begin, begin + count, R):
                 r = min(R, begin + count - b)
-                if spd:
+                if vec:
+                    rows = ops.vector_all_pairs_dist(table, man.model_name, self.scale.detach(), self.scale_coef, b, r, out=dbuf[:r])
+                elif spd:
                     rows = self.distance_matrix(b, r)
                 else:
                     rows = ops.all_pairs_dist(table, man.model_name, man.metric.kind.value, weights, self.scale.detach(),

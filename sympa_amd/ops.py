@@ -1497,6 +1497,219 @@ def spd_rsgd_step_(table, grad, lr, weight_decay=0.0, clip_sqnorm=None, max_norm
 
 
 # ---------------------------------------------------------------------------------------------------
+# Vector models (C-ABI sympa_vector_*): points are rows of `dims` doubles
+# ---------------------------------------------------------------------------------------------------
+VECTOR_MODEL_IDS = {"euclidean": 0, "poincare": 1, "lorentz": 2, "sphere": 3, "prod-hysph": 4, "prod-hyhy": 5, "prod-hyeu": 6,
+                    "prod-sphsph": 7}
+VECTOR_MAX_DIMS = 1024
+# factor geometries per model: E, P, L, S; a product splits the row into two halves
+VECTOR_FACTORS = {"euclidean": "E", "poincare": "P", "lorentz": "L", "sphere": "S", "prod-hysph": "PS", "prod-hyhy": "PP",
+                  "prod-hyeu": "PE", "prod-sphsph": "SS"}
+
+
+def vector_check_dims(model, dims):
+    """ValueError unless `dims` coordinates can hold a point of `model` (products: even dims; S and L factors: >= 2 coordinates)."""
+    if model not in VECTOR_MODEL_IDS:
+        raise ValueError(f"unknown vector model {model!r}")
+    factors = VECTOR_FACTORS[model]
+    if dims < 1 or dims > VECTOR_MAX_DIMS:
+        raise ValueError(f"{model}: dims must be in [1, {VECTOR_MAX_DIMS}], got {dims}")
+    if len(factors) == 2 and dims % 2:
+        raise ValueError(f"{model}: a product manifold needs even dims (each factor gets half), got {dims}")
+    m = dims // len(factors)
+    if any(g in "SL" for g in factors) and m < 2:
+        raise ValueError(f"{model}: a sphere / lorentz factor needs at least 2 coordinates, got {m}")
+
+
+def _vec_rows(t, name):
+    _need_gpu(t, name)
+    if t.dtype != torch.float64 or t.dim() != 2:
+        raise ValueError(f"{name} must be a float64 [b, dims] tensor, got {tuple(t.shape)} {t.dtype}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _vec_triplets(triplets):
+    _need_gpu(triplets, "triplets")
+    if triplets.dtype != torch.int64 or triplets.dim() != 2 or triplets.shape[1] < 2:
+        raise TypeError("triplets must be an int64 [b, >=2] tensor")
+    if triplets.stride(1) != 1:
+        triplets = triplets.contiguous()
+    b = triplets.shape[0]
+    return triplets, b, (triplets.stride(0) if b > 1 else triplets.shape[1])
+
+
+def _vec_scale(scale, dev):
+    if scale is None:
+        return None
+    return scale.detach().reshape(-1)[:1].to(device=dev, dtype=torch.float64).contiguous()
+
+
+def vector_dist_forward(x, y, model):
+    """manifold.dist on rows of x, y [b, dims] (C-ABI sympa_vector_dist_fwd)."""
+    lib = _lib.load()
+    x, y = _vec_rows(x.detach(), "x"), _vec_rows(y.detach(), "y")
+    if x.shape != y.shape:
+        raise ValueError(f"expected two [b, dims] tensors of one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    vector_check_dims(model, x.shape[1])
+    out = torch.empty(x.shape[0], dtype=torch.float64, device=x.device)
+    st = _status_buf(x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.sympa_vector_dist_fwd(x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], VECTOR_MODEL_IDS[model], out.data_ptr(),
+                                       st.data_ptr(), 0, _stream())
+    _lib.check(rc)
+    if _debug:
+        check_status(x.device)
+    return out
+
+
+def vector_model_forward(table, triplets, model, scale=None, scale_coef=1.0, out=None):
+    """Model.forward of a vector model over a [N, dims] table (C-ABI sympa_vector_model_forward)."""
+    lib = _lib.load()
+    tab = _vec_rows(table.detach(), "table")
+    vector_check_dims(model, tab.shape[1])
+    triplets, b, stride = _vec_triplets(triplets)
+    if out is None:
+        out = torch.empty(b, dtype=torch.float64, device=tab.device)
+    if b == 0:
+        return out
+    sc = _vec_scale(scale, tab.device)
+    st = _status_buf(tab.device)
+    tp = triplets.data_ptr()
+    with torch.cuda.device(tab.device):
+        rc = lib.sympa_vector_model_forward(tab.data_ptr(), tab.shape[0], tab.shape[1], tp, stride, tp + 8, stride, b,
+                                            VECTOR_MODEL_IDS[model], None if sc is None else sc.data_ptr(), float(scale_coef),
+                                            out.data_ptr(), st.data_ptr(), 0, _stream())
+    _lib.check(rc)
+    if _debug:
+        check_status(tab.device)
+    return out
+
+
+def vector_all_pairs_dist(table, model, scale=None, scale_coef=1.0, row_begin=0, row_count=None, out=None):
+    """Rows [row_begin, row_begin + row_count) of the N x N distance matrix of a vector model (C-ABI
+    sympa_vector_all_pairs_dist): no pair list, diagonal exactly 0, (i, j) bit-equal to (j, i)."""
+    lib = _lib.load()
+    tab = _vec_rows(table.detach(), "table")
+    vector_check_dims(model, tab.shape[1])
+    N = tab.shape[0]
+    row_count = N - row_begin if row_count is None else row_count
+    if row_begin < 0 or row_count < 0 or row_begin + row_count > N:
+        raise ValueError(f"rows [{row_begin}, {row_begin + row_count}) are outside the table's {N}")
+    if out is None:
+        out = torch.empty(row_count, N, dtype=torch.float64, device=tab.device)
+    elif out.dtype != torch.float64 or out.shape != (row_count, N) or not out.is_contiguous() or out.device != tab.device:
+        raise ValueError(f"out must be a contiguous float64 [{row_count}, {N}] tensor on {tab.device}")
+    if row_count == 0 or N == 0:
+        return out
+    sc = _vec_scale(scale, tab.device)
+    st = _status_buf(tab.device)
+    with torch.cuda.device(tab.device):
+        rc = lib.sympa_vector_all_pairs_dist(tab.data_ptr(), N, tab.shape[1], int(row_begin), int(row_count), VECTOR_MODEL_IDS[model],
+                                             None if sc is None else sc.data_ptr(), float(scale_coef), out.data_ptr(),
+                                             st.data_ptr(), 0, _stream())
+    _lib.check(rc)
+    if _debug:
+        check_status(tab.device)
+    return out
+
+
+def vector_backward_rows(x, y, model, triplets=None, grad_out=None, graph_dist=None, scale=None, scale_coef=1.0, loss_scale=1.0,
+                         loss=None, grad_scale=None, rows=None, want_out=False):
+    """Backward of a vector model's distance (C-ABI sympa_vector_backward_rows), shaped like spd_backward_rows.  triplets None:
+    pair i = (x[i], y[i]); otherwise x is y is the [N, dims] table.  Give grad_out [b] or graph_dist [b] (fused
+    AverageDistortionLoss, accumulated into `loss`).  Returns (rows [2b, dims], out or None): rows [0, b) are the gradient rows of
+    the first points, [b, 2b) of the second."""
+    lib = _lib.load()
+    x, y = _vec_rows(x.detach(), "x"), _vec_rows(y.detach(), "y")
+    dims, dev = x.shape[1], x.device
+    vector_check_dims(model, dims)
+    if y.shape[1] != dims:
+        raise ValueError("x and y must have the same dims")
+    if triplets is not None:
+        triplets, b, stride = _vec_triplets(triplets)
+        sp, dp = triplets.data_ptr(), triplets.data_ptr() + 8
+    else:
+        if x.shape != y.shape:
+            raise ValueError("x and y must have one shape when no triplets are given")
+        b, stride, sp, dp = x.shape[0], 0, None, None
+    if rows is None:
+        rows = torch.empty(2 * b, dims, dtype=torch.float64, device=dev)
+    elif rows.dtype != torch.float64 or rows.numel() < 2 * b * dims or not rows.is_contiguous() or rows.device != dev:
+        raise ValueError("rows buffer too small, not contiguous, or not float64 on the table's device")
+    out = torch.empty(b, dtype=torch.float64, device=dev) if want_out else None
+    if b == 0:
+        return rows, out
+    if grad_out is None and graph_dist is None:
+        raise ValueError("give grad_out or graph_dist")
+    go = None if grad_out is None else grad_out.detach().to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+    gd = None if graph_dist is None else graph_dist.detach().to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+    for t, name in ((go, "grad_out"), (gd, "graph_dist")):
+        if t is not None and t.numel() != b:
+            raise ValueError(f"{name} must have {b} entries, got {t.numel()}")
+    sc = _vec_scale(scale, dev)
+    st = _status_buf(dev)
+    with torch.cuda.device(dev):
+        rc = lib.sympa_vector_backward_rows(
+            x.data_ptr(), y.data_ptr(), x.shape[0], dims, VECTOR_MODEL_IDS[model], sp, stride, dp, stride, b,
+            None if sc is None else sc.data_ptr(), float(scale_coef), None if go is None else go.data_ptr(),
+            None if gd is None else gd.data_ptr(), float(loss_scale), None if loss is None else loss.data_ptr(), rows.data_ptr(),
+            rows.data_ptr() + b * dims * 8, None if grad_scale is None else grad_scale.data_ptr(),
+            None if out is None else out.data_ptr(), st.data_ptr(), 0, _stream())
+    _lib.check(rc)
+    if _debug:
+        check_status(dev)
+    return rows, out
+
+
+def vector_egrad2rgrad(x, u, model):
+    lib = _lib.load()
+    x, u = _vec_rows(x.detach(), "x"), _vec_rows(u.detach(), "u")
+    if x.shape != u.shape:
+        raise ValueError("x and u must have one shape")
+    vector_check_dims(model, x.shape[1])
+    out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        rc = lib.sympa_vector_egrad2rgrad(x.data_ptr(), u.data_ptr(), x.shape[0], x.shape[1], VECTOR_MODEL_IDS[model], out.data_ptr(),
+                                          _stream())
+    _lib.check(rc)
+    return out
+
+
+def vector_projx(x, model, counter=None):
+    lib = _lib.load()
+    x = _vec_rows(x.detach(), "x")
+    vector_check_dims(model, x.shape[1])
+    out = torch.empty_like(x)
+    st = _status_buf(x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.sympa_vector_projx(x.data_ptr(), x.shape[0], x.shape[1], VECTOR_MODEL_IDS[model], out.data_ptr(),
+                                    None if counter is None else counter.data_ptr(), st.data_ptr(), _stream())
+    _lib.check(rc)
+    return out
+
+
+def vector_rsgd_step_(table, grad, model, lr, weight_decay=0.0, counter=None, clip_sqnorm=None, max_norm=None):
+    """In-place geoopt RiemannianSGD step (momentum 0) over a vector model's table (C-ABI sympa_vector_rsgd_step)."""
+    lib = _lib.load()
+    _need_gpu(table, "table")
+    if not table.is_contiguous():
+        raise ValueError("table must be contiguous for the in-place step")
+    grad = _vec_rows(grad.detach(), "grad")
+    if table.dtype != torch.float64 or table.dim() != 2 or table.shape != grad.shape:
+        raise ValueError(f"table must be a float64 [N, dims] tensor of the gradient's shape {tuple(grad.shape)}, got "
+                         f"{tuple(table.shape)} {table.dtype}")
+    vector_check_dims(model, table.shape[1])
+    st = _status_buf(table.device)
+    with torch.cuda.device(table.device):
+        rc = lib.sympa_vector_rsgd_step(table.data_ptr(), grad.data_ptr(), table.shape[0], table.shape[1], VECTOR_MODEL_IDS[model],
+                                        float(lr), float(weight_decay), None if clip_sqnorm is None else clip_sqnorm.data_ptr(),
+                                        float(max_norm) if max_norm is not None else 0.0,
+                                        None if counter is None else counter.data_ptr(), st.data_ptr(), _stream())
+    _lib.check(rc)
+    return table
+
+
+# ---------------------------------------------------------------------------------------------------
 # Mean average precision (C-ABI sympa_map_rows; reference sympa/metrics.py:25-63, runner.py:137-154)
 # ---------------------------------------------------------------------------------------------------
 FLAG_FP32_KEYS = 256   # map_rows: round every distance to fp32 before comparing (the reference's float32 matrix)

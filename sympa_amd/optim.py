@@ -12,6 +12,7 @@ import torch
 from sympa_amd import ops
 from sympa_amd.manifolds.siegel_manifold import SiegelManifold
 from sympa_amd.manifolds.spd import SymmetricPositiveDefinite
+from sympa_amd.manifolds.vector import VectorManifold
 
 
 class RiemannianSGD(torch.optim.Optimizer):
@@ -63,6 +64,12 @@ class RiemannianSGD(torch.optim.Optimizer):
                     # geoopt's SPD step: retr(x, -lr x sym(g + wd x) x), one kernel over the table
                     ops.spd_rsgd_step_(p.data, p.grad, lr, wd, clip_sqnorm=sq,
                                        max_norm=self.clip_max_norm if sq is not None else None)
+                elif isinstance(manifold, VectorManifold) and p.is_cuda:
+                    if p.dtype != torch.float64:
+                        raise TypeError("a vector model's table must be float64 (config.py:17-18)")
+                    # per factor: retr(x, -lr egrad2rgrad(x, g + wd x)), one kernel over the table; rescaled Poincare rows are counted
+                    ops.vector_rsgd_step_(p.data, p.grad, manifold.model_name, lr, wd, counter=manifold.projected_counter(p.device),
+                                          clip_sqnorm=sq, max_norm=self.clip_max_norm if sq is not None else None)
                 elif isinstance(manifold, SiegelManifold) and p.is_cuda and sq is not None:
                     ops.rsgd_step_(p.data, p.grad, manifold.model_name, lr, wd, counter=manifold.projected_counter(p.device),
                                    clip_sqnorm=sq, max_norm=self.clip_max_norm)
@@ -185,6 +192,9 @@ class RiemannianAdam(torch.optim.Optimizer):
                     ops.table_changed(p)       # (see RiemannianSGD.step)
                 if isinstance(manifold, SymmetricPositiveDefinite):
                     raise NotImplementedError("RiemannianAdam on the spd model needs geoopt's parallel transport: use rsgd")
+                if isinstance(manifold, VectorManifold):
+                    raise NotImplementedError("RiemannianAdam on the vector models needs their parallel transports, which are not "
+                                              "built: use rsgd")
                 state = self._init_param_state(p, (b1, b2), group["step"] - 1)
                 m, v = state["exp_avg"], state["exp_avg_sq"]
                 pows = state["bias_pows"].mul_(state["betas"])      # (b1^t, b2^t), t = steps this parameter has taken: one launch

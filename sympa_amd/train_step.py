@@ -78,6 +78,10 @@ class GraphedTrainStep:
         if not getattr(optimizer, "graph_capturable", False):
             raise TypeError(f"{type(optimizer).__name__} cannot be captured in a hipGraph (its step() changes host-side state "
                             "every call); use sympa_amd.optim.RiemannianSGD / RiemannianAdam or run the step eagerly")
+        if getattr(model.manifold, "model_name", None) in ops.VECTOR_MODEL_IDS:
+            raise NotImplementedError(f"GraphedTrainStep is not built for the vector models ('{model.manifold.model_name}'): run the "
+                                      "classic loop -- Model.fused_loss_backward (or forward + loss + backward), then "
+                                      "RiemannianSGD.step (DESIGN.md section 19)")
         self.model, self.opt = model, optimizer
         self.batch_size, self.max_grad_norm = int(batch_size), float(max_grad_norm)
         self.device = torch.device(device)

@@ -128,7 +128,10 @@ def train(args, log=print):
     # single GPU: the whole step is one hipGraph replay
     graphed = GraphedTrainStep(model, opt, batch, args.max_grad_norm, dev,
                                deterministic=True if args.deterministic else None, accumulate_loss=True) \
-        if (world == 1 and args.graph_step and args.grad_exchange == "none") else None
+        if (world == 1 and args.graph_step and args.grad_exchange == "none" and args.manifold not in ops.VECTOR_MODEL_IDS) else None
+    # (the vector models train through the classic loop below: fused loss + backward rows + scatter, clip, RiemannianSGD.step)
+    if args.manifold in ops.VECTOR_MODEL_IDS and (world > 1 or args.grad_exchange != "none"):
+        raise SystemExit(f"--manifold {args.manifold}: the gradient exchange is not wired to the vector models (single GPU only)")
     # (RiemannianAdam keeps its powers b^t in device words, so its step is captured too -- as the same two kernels where the
     # table qualifies: sympa_radam_step_fused)
     # N > 1 (or --grad_exchange given): gradients live in one persistent flat buffer; the table gradient travels dense
