@@ -572,6 +572,22 @@ int sympa_vector_projx(const double* x, int64_t b, int dims, int model, double* 
                        void* stream);
 int sympa_vector_rsgd_step(double* table, const double* grad, int64_t num_rows, int dims, int model, double lr, double weight_decay,
                            const double* total_sqnorm, double max_norm, int32_t* projected_count, int32_t* status, void* stream);
+/* One geoopt.optim.RiemannianAdam step (geoopt optim/radam.py; train.py:69-70: `--optim radam`, eps = 1e-7) over the table in
+ * place, as one kernel (geoopt is not in the reference tree: PARITY UNPINNED, pinned to 50-digit
+ * evaluations of the project's definitions, tests/golden/exact_vector_*_radam*.npz).  Per factor
+ *     g = coef grad + weight_decay x,  r = egrad2rgrad(x, g),  m1 = beta1 m + (1 - beta1) r,  s1 = beta2 s + (1 - beta2) I(x, r),
+ *     y = retr(x, -lr (m1 / (1 - beta1^t)) / (sqrt(s1 / (1 - beta2^t)) + eps_adam)),
+ *     table <- y,  exp_avg <- the parallel transport of m1 from x to y,  exp_avg_sq <- s1,
+ * I = geoopt's component_inner: r_i^2 per coordinate for a euclidean factor; one value per factor otherwise (poincare
+ * (2 / (1 - xx))^2 sum r_i^2, sphere sum r_i^2, lorentz max(<r, r>_L, 0)), held in every coordinate of the factor: exp_avg and
+ * exp_avg_sq are [num_rows, dims] like the table, and the incoming value of a factor is read at its first coordinate.
+ * bias_pows: device pair (beta1^t, beta2^t) of this step, as for sympa_radam_step; total_sqnorm / max_norm: the folded clip,
+ * projected_count and status as for sympa_vector_rsgd_step.  num_rows == 0 is a no-op; a null table / grad / exp_avg /
+ * exp_avg_sq / bias_pows, a beta outside [0, 1) or eps_adam <= 0 is SYMPA_ERR_BAD_ARG. */
+int sympa_vector_radam_step(double* table, const double* grad, double* exp_avg, double* exp_avg_sq, int64_t num_rows, int dims,
+                            int model, double lr, double beta1, double beta2, double eps_adam, double weight_decay,
+                            const double* bias_pows, const double* total_sqnorm, double max_norm, int32_t* projected_count,
+                            int32_t* status, void* stream);
 
 /* Per-row average precision of a block of rows of the all-pairs distance matrix: the ranking half of
  * MeanAveragePrecisionMetric.calculate_metric (sympa/metrics.py:39-63) over the matrix Runner.calculate_mAP builds

@@ -72,6 +72,7 @@ SYMBOLS = (
     "sympa_vector_egrad2rgrad",
     "sympa_vector_projx",
     "sympa_vector_rsgd_step",
+    "sympa_vector_radam_step",
     "sympa_map_workspace_bytes",
     "sympa_map_rows",
     "sympa_graph_hops_workspace_bytes",
@@ -311,6 +312,10 @@ def load():
     lib.sympa_vector_rsgd_step.restype = C.c_int
     lib.sympa_vector_rsgd_step.argtypes = [_c_double_p, _c_double_p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double,
                                            _c_double_p, C.c_double, _c_i32_p, _c_i32_p, C.c_void_p]
+    lib.sympa_vector_radam_step.restype = C.c_int
+    lib.sympa_vector_radam_step.argtypes = [_c_double_p, _c_double_p, _c_double_p, _c_double_p, C.c_int64, C.c_int, C.c_int,
+                                            C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _c_double_p, _c_double_p,
+                                            C.c_double, _c_i32_p, _c_i32_p, C.c_void_p]
     lib.sympa_table_pack_bytes.restype = C.c_int64
     lib.sympa_table_pack_bytes.argtypes = [C.c_int64, C.c_int, C.c_int]
     lib.sympa_table_pack.restype = C.c_int

@@ -1,6 +1,6 @@
 // Arithmetic of the vector models: euclidean, poincare, lorentz, sphere and the four products of two
-// of them.  Compiles under hipcc (vector_models.hip) and under g++ (tests/hostsim/hostsim_vector.cpp), like the other
-// *_math.hpp headers.  A point is a row of `dims` doubles split into one or two factors; every kernel is
+// of them, and their RiemannianAdam row (section 20).  Compiles under hipcc (vector_models.hip) and under g++
+// (tests/hostsim/hostsim_vector.cpp, tests/hostsim/hostsim_vector_radam.cpp), like the other *_math.hpp headers.  A point is a row of `dims` doubles split into one or two factors; every kernel is
 //     per-lane sums over the lane's coordinates  ->  fixed xor butterfly over the G lanes of the pair / row
 //     ->  scalar epilogue (the only place where the geometry is looked at)  ->  per-coordinate output.
 // The pieces below are those four; the butterfly itself belongs to the caller (shuffles on the device, a loop on the host).
@@ -69,7 +69,10 @@ SYMPA_HD int vec_lanes(int dims) {
 
 // Coordinate i of the row: its factor, and J_i (-1 for the time-like coordinate of an L factor, else 1).
 SYMPA_HD int vec_factor_of(const VecLayout& L, int i) { return (L.nf == 2 && i >= L.begin[1]) ? 1 : 0; }
-SYMPA_HD double vec_sign(const VecLayout& L, int f, int i) { return (L.geom[f] == VG_L && i == L.begin[f]) ? -1.0 : 1.0; }
+// (selects, not indexed loads: a layout indexed by a runtime factor would be copied out of the kernel arguments)
+SYMPA_HD int vec_geom(const VecLayout& L, int f) { return f ? L.geom[1] : L.geom[0]; }
+SYMPA_HD int vec_begin(const VecLayout& L, int f) { return f ? L.begin[1] : L.begin[0]; }
+SYMPA_HD double vec_sign(const VecLayout& L, int f, int i) { return (vec_geom(L, f) == VG_L && i == vec_begin(L, f)) ? -1.0 : 1.0; }
 
 // Lane `lane` of G owns the coordinate pairs (2c, 2c + 1), c = lane, lane + G, ...: consecutive lanes read consecutive 16 bytes.
 // The assignment does not depend on how the coordinates are loaded, so a pair's sums are the same bits in every entry point.
@@ -209,7 +212,7 @@ SYMPA_HD double vec_row_grad(double grad, double x, double coef, double wd) { re
 // egrad2rgrad of one coordinate from the round-1 sums
 SYMPA_HD double vec_row_rgrad(const VecLayout& L, const VecRowSums& s, int i, double x, double g) {
     const int f = vec_factor_of(L, i);
-    const int geom = L.geom[f];
+    const int geom = vec_geom(L, f);
     const double xx = f ? s.xx[1] : s.xx[0], xg = f ? s.xg[1] : s.xg[0];
     if (geom == VG_P) {
         const double a = 1.0 - xx;
@@ -224,7 +227,7 @@ SYMPA_HD double vec_row_rgrad(const VecLayout& L, const VecRowSums& s, int i, do
 SYMPA_HD double vec_row_stage1(const VecLayout& L, const VecRowSums& s, int i, double x, double g, double lr) {
     const int f = vec_factor_of(L, i);
     const double r = vec_row_rgrad(L, s, i, x, g);
-    return L.geom[f] == VG_L ? -lr * r : d_fma(-lr, r, x);
+    return vec_geom(L, f) == VG_L ? -lr * r : d_fma(-lr, r, x);
 }
 
 // what stage 2 needs of a factor, from ww = sum J_i w_i^2:  P: the rescale (1 when the point stays inside), S: 1 / |z|,
@@ -235,8 +238,9 @@ struct VecRowStep {
 
 SYMPA_HD void vec_row_step_coef(const VecLayout& L, const double (&ww)[VEC_MAX_FACTORS], VecRowStep& c, bool& moved) {
     for (int f = 0; f < VEC_MAX_FACTORS; ++f) { c.a[f] = 1.0; c.b[f] = 0.0; }
-    for (int f = 0; f < L.nf; ++f) {
-        const int geom = L.geom[f];
+    for (int f = 0; f < VEC_MAX_FACTORS; ++f) {
+        if (f >= L.nf) continue;
+        const int geom = vec_geom(L, f);
         if (geom == VG_P) {
             const double nrm = std::sqrt(ww[f]);
             if (nrm > 1.0 - VEC_BALL_EPS) { c.a[f] = (1.0 - VEC_BALL_EPS) / nrm; moved = true; }
@@ -254,17 +258,18 @@ SYMPA_HD void vec_row_step_coef(const VecLayout& L, const double (&ww)[VEC_MAX_F
 SYMPA_HD double vec_row_stage2(const VecLayout& L, const VecRowStep& c, int i, double x, double w) {
     const int f = vec_factor_of(L, i);
     const double a = f ? c.a[1] : c.a[0], b = f ? c.b[1] : c.b[0];
-    return L.geom[f] == VG_L ? d_fma(a, x, b * w) : a * w;
+    return vec_geom(L, f) == VG_L ? d_fma(a, x, b * w) : a * w;
 }
 
 // projx of one coordinate from the round-1 sums of the row itself (`moved` as above)
 SYMPA_HD void vec_row_projx_coef(const VecLayout& L, const VecRowSums& s, VecRowStep& c, bool& moved) {
     for (int f = 0; f < VEC_MAX_FACTORS; ++f) { c.a[f] = 1.0; c.b[f] = 0.0; }
-    for (int f = 0; f < L.nf; ++f) {
-        if (L.geom[f] == VG_P) {
+    for (int f = 0; f < VEC_MAX_FACTORS; ++f) {
+        if (f >= L.nf) continue;
+        if (vec_geom(L, f) == VG_P) {
             const double nrm = std::sqrt(s.xx[f]);
             if (nrm > 1.0 - VEC_BALL_EPS) { c.a[f] = (1.0 - VEC_BALL_EPS) / nrm; moved = true; }
-        } else if (L.geom[f] == VG_S) {
+        } else if (vec_geom(L, f) == VG_S) {
             c.a[f] = 1.0 / std::sqrt(s.xx[f]);
         }
     }
@@ -273,15 +278,178 @@ SYMPA_HD void vec_row_projx_coef(const VecLayout& L, const VecRowSums& s, VecRow
 // the time-like coordinate of an L factor after a step or a projx: sqrt(1 + rest); every other coordinate is `v`
 SYMPA_HD double vec_row_final(const VecLayout& L, const double (&rest)[VEC_MAX_FACTORS], int i, double v) {
     const int f = vec_factor_of(L, i);
-    if (L.geom[f] == VG_L && i == L.begin[f]) return std::sqrt(1.0 + (f ? rest[1] : rest[0]));
+    if (vec_geom(L, f) == VG_L && i == vec_begin(L, f)) return std::sqrt(1.0 + (f ? rest[1] : rest[0]));
     return v;
 }
 
 // A row is off the manifold or not finite: the status bits of its final round-1 sums (P: xx >= 1)
 SYMPA_HD int vec_row_status(const VecLayout& L, const VecRowSums& s) {
     int st = 0;
-    for (int f = 0; f < L.nf; ++f) {
+    for (int f = 0; f < VEC_MAX_FACTORS; ++f) {
+        if (f >= L.nf) continue;
         if (!(s.xx[f] - s.xx[f] == 0.0) || !(s.xg[f] - s.xg[f] == 0.0)) st |= ST_NONFINITE;
+    }
+    return st;
+}
+
+// ---- the RiemannianAdam row (geoopt optim/radam.py per factor):
+//     g = coef grad + wd x,   r = egrad2rgrad(x, g),   m1 = b1 m + (1 - b1) r,   s1 = b2 s + (1 - b2) I(x, r),
+//     u = -lr (m1 / (1 - b1^t)) / (sqrt(s1 / (1 - b2^t)) + eps),   y = retr(x, u),   m' = T(x -> y, m1)
+// I is geoopt's component_inner: per coordinate for E, one value per factor for P, S, L (held in every coordinate of the
+// factor; the incoming value is read at the factor's first coordinate).  Rounds of sums: round 1 as above (xx, xg);
+// round 2: rr = sum J_i r_i^2, xm = <x, m1>, mm = sum J_i m1_i^2 -- the norm of the stage-1 coordinates follows from them and
+// xx without a round of its own (u = c m1 with one c per factor); round 3 (only with an L factor): the new time coordinate;
+// round 4: the transport's inner products on the row as stored.
+struct VecAdamParams {
+    double lr, beta1, beta2, eps, wd, coef;
+    double bc1, bc2;       // the bias corrections 1 - beta1^t, 1 - beta2^t
+};
+
+struct VecAdamCoord {
+    double x, r, m1, s;    // s: the incoming exp_avg_sq of the coordinate
+};
+
+SYMPA_HD void vec_adam_coord(const VecLayout& L, const VecRowSums& rs, const VecAdamParams& P, int i, double x, double grad, double m,
+                             double s, VecAdamCoord& c) {
+    c.x = x;
+    c.r = vec_row_rgrad(L, rs, i, x, vec_row_grad(grad, x, P.coef, P.wd));
+    c.m1 = d_fma(P.beta1, m, (1.0 - P.beta1) * c.r);
+    c.s = s;
+}
+
+struct VecAdamSums {
+    double rr[VEC_MAX_FACTORS], xm[VEC_MAX_FACTORS], mm[VEC_MAX_FACTORS], sin[VEC_MAX_FACTORS];
+};
+
+SYMPA_HD void vec_adam_sums_zero(VecAdamSums& S) {
+    for (int f = 0; f < VEC_MAX_FACTORS; ++f) { S.rr[f] = 0.0; S.xm[f] = 0.0; S.mm[f] = 0.0; S.sin[f] = 0.0; }
+}
+
+// `sin` is the incoming s of the factor's first coordinate: its owner adds it to zeros, so the butterfly hands every lane its bits
+SYMPA_HD void vec_adam_accumulate(const VecLayout& L, int i, const VecAdamCoord& c, VecAdamSums& S) {
+    const int f = vec_factor_of(L, i);
+    const bool first = i == (f ? L.begin[1] : L.begin[0]);
+    const double j = vec_sign(L, f, i);
+    const double rr = d_fma(j * c.r, c.r, f ? S.rr[1] : S.rr[0]);
+    const double xm = d_fma(c.x, c.m1, f ? S.xm[1] : S.xm[0]);
+    const double mm = d_fma(j * c.m1, c.m1, f ? S.mm[1] : S.mm[0]);
+    const double sin = first ? c.s : (f ? S.sin[1] : S.sin[0]);
+    if (f) { S.rr[1] = rr; S.xm[1] = xm; S.mm[1] = mm; S.sin[1] = sin; } else { S.rr[0] = rr; S.xm[0] = xm; S.mm[0] = mm; S.sin[0] = sin; }
+}
+
+// u = c m1:  c = -(lr / (1 - b1^t)) / (sqrt(s1 / (1 - b2^t)) + eps)
+SYMPA_HD double vec_adam_scale(const VecAdamParams& P, double s1) { return -(P.lr / P.bc1) / (std::sqrt(s1 / P.bc2) + P.eps); }
+
+// what the coordinates need of a P, S or L factor: s1, c, and ww = sum J_i w_i^2 of the stage-1 coordinates w (E, P, S:
+// w = x + c m1, ww = xx + 2 c xm + c^2 mm;  L: w = c m1, ww = c^2 mm), which vec_row_step_coef takes.  An E factor keeps
+// s1 and c per coordinate.
+struct VecAdamStep {
+    double s1[VEC_MAX_FACTORS], c[VEC_MAX_FACTORS];
+};
+
+SYMPA_HD void vec_adam_step(const VecLayout& L, const VecRowSums& rs, const VecAdamSums& S, const VecAdamParams& P, VecAdamStep& a,
+                            double (&ww)[VEC_MAX_FACTORS]) {
+    for (int f = 0; f < VEC_MAX_FACTORS; ++f) { a.s1[f] = 0.0; a.c[f] = 0.0; ww[f] = 0.0; }
+    for (int f = 0; f < VEC_MAX_FACTORS; ++f) {
+        if (f >= L.nf) continue;
+        const int geom = vec_geom(L, f);
+        if (geom == VG_E) continue;
+        double inner = S.rr[f];
+        if (geom == VG_P) {
+            const double lam = 2.0 / (1.0 - rs.xx[f]);
+            inner = lam * lam * S.rr[f];
+        } else if (geom == VG_L) {
+            inner = S.rr[f] > 0.0 ? S.rr[f] : (S.rr[f] == S.rr[f] ? 0.0 : S.rr[f]);
+        }
+        a.s1[f] = d_fma(P.beta2, S.sin[f], (1.0 - P.beta2) * inner);
+        a.c[f] = vec_adam_scale(P, a.s1[f]);
+        const double c = a.c[f];
+        ww[f] = geom == VG_L ? (c * c) * S.mm[f] : d_fma(c * c, S.mm[f], d_fma(2.0 * c, S.xm[f], rs.xx[f]));
+    }
+}
+
+// the new exp_avg_sq of one coordinate
+SYMPA_HD double vec_adam_s1(const VecLayout& L, const VecAdamStep& a, const VecAdamParams& P, int i, const VecAdamCoord& c) {
+    const int f = vec_factor_of(L, i);
+    if (vec_geom(L, f) == VG_E) return d_fma(P.beta2, c.s, (1.0 - P.beta2) * (c.r * c.r));
+    return f ? a.s1[1] : a.s1[0];
+}
+
+// stage 1 (the RSGD row's, with u in place of -lr r): E, P, S: x + u;  L: u
+SYMPA_HD double vec_adam_stage1(const VecLayout& L, const VecAdamStep& a, const VecAdamParams& P, int i, const VecAdamCoord& c) {
+    const int f = vec_factor_of(L, i);
+    const int geom = vec_geom(L, f);
+    const double cc = geom == VG_E ? vec_adam_scale(P, vec_adam_s1(L, a, P, i, c)) : (f ? a.c[1] : a.c[0]);
+    return geom == VG_L ? cc * c.m1 : d_fma(cc, c.m1, c.x);
+}
+
+// ---- parallel transport T(x -> y, w) of w = m1 along the step, y = the row as stored, in forms that are the identity at
+// y = x without a 0 / 0:
+//     E: w      S: w - <y, w> y      L: w + <y, w>_L / (2 + dd_L / 2) (x + y),  dd_L = sum J_i (x_i - y_i)^2  (= 1 - <x, y>_L)
+//     P: (1 - yy) / (1 - xx) gyr[y, -x] w,   gyr[a, b] w = w + 2 (A a + B b) / D,   A = -<a, w> bb + <b, w> + 2 <a, b> <b, w>,
+//        B = -<b, w> aa - <a, w>,   D = 1 + 2 <a, b> + aa bb
+// Round-4 sums: ym = sum J_i y_i w_i;  xy = <x, y> (P) or dd_L (L);  yy.
+struct VecTranspSums {
+    double ym[VEC_MAX_FACTORS], xy[VEC_MAX_FACTORS], yy[VEC_MAX_FACTORS];
+};
+
+SYMPA_HD void vec_transp_sums_zero(VecTranspSums& T) {
+    for (int f = 0; f < VEC_MAX_FACTORS; ++f) { T.ym[f] = 0.0; T.xy[f] = 0.0; T.yy[f] = 0.0; }
+}
+
+SYMPA_HD void vec_transp_accumulate(const VecLayout& L, int i, double x, double y, double w, VecTranspSums& T) {
+    const int f = vec_factor_of(L, i);
+    const double j = vec_sign(L, f, i);
+    const double t = x - y;
+    const double ym = d_fma(j * y, w, f ? T.ym[1] : T.ym[0]);
+    const double xy = vec_geom(L, f) == VG_L ? d_fma(j * t, t, f ? T.xy[1] : T.xy[0]) : d_fma(x, y, f ? T.xy[1] : T.xy[0]);
+    const double yy = d_fma(y, y, f ? T.yy[1] : T.yy[0]);
+    if (f) { T.ym[1] = ym; T.xy[1] = xy; T.yy[1] = yy; } else { T.ym[0] = ym; T.xy[0] = xy; T.yy[0] = yy; }
+}
+
+// m'_i = t0 (w_i + ta y_i + tb x_i)
+struct VecTransp {
+    double t0[VEC_MAX_FACTORS], ta[VEC_MAX_FACTORS], tb[VEC_MAX_FACTORS];
+};
+
+// xx = <x, x> and xw = <x, w> of the factor (round 1 and round 2)
+SYMPA_HD void vec_transp_coef(const VecLayout& L, const double (&xx)[VEC_MAX_FACTORS], const double (&xw)[VEC_MAX_FACTORS],
+                              const VecTranspSums& T, VecTransp& c) {
+    for (int f = 0; f < VEC_MAX_FACTORS; ++f) { c.t0[f] = 1.0; c.ta[f] = 0.0; c.tb[f] = 0.0; }
+    for (int f = 0; f < VEC_MAX_FACTORS; ++f) {
+        if (f >= L.nf) continue;
+        const int geom = vec_geom(L, f);
+        if (geom == VG_S) {
+            c.ta[f] = -T.ym[f];
+        } else if (geom == VG_L) {
+            const double k = T.ym[f] / d_fma(0.5, T.xy[f], 2.0);
+            c.ta[f] = k; c.tb[f] = k;
+        } else if (geom == VG_P) {
+            // a = y, b = -x:  <a, w> = ym, <b, w> = -xw, <a, b> = -xy, aa = yy, bb = xx
+            const double ym = T.ym[f], xy = T.xy[f], yy = T.yy[f];
+            const double A = d_fma(2.0 * xy, xw[f], d_fma(-ym, xx[f], -xw[f]));
+            const double B = d_fma(xw[f], yy, -ym);
+            const double D = d_fma(yy, xx[f], d_fma(-2.0, xy, 1.0));
+            c.t0[f] = (1.0 - yy) / (1.0 - xx[f]);
+            c.ta[f] = 2.0 * A / D;
+            c.tb[f] = -2.0 * B / D;
+        }
+    }
+}
+
+SYMPA_HD double vec_transp_coord(const VecLayout& L, const VecTransp& c, int i, double x, double y, double w) {
+    const int f = vec_factor_of(L, i);
+    if (vec_geom(L, f) == VG_E) return w;
+    return (f ? c.t0[1] : c.t0[0]) * d_fma(f ? c.ta[1] : c.ta[0], y, d_fma(f ? c.tb[1] : c.tb[0], x, w));
+}
+
+// non-finite sums of the Adam row (round 1 is vec_row_status)
+SYMPA_HD int vec_adam_status(const VecLayout& L, const VecAdamSums& S, const double (&ww)[VEC_MAX_FACTORS], const VecTranspSums& T) {
+    int st = 0;
+    for (int f = 0; f < VEC_MAX_FACTORS; ++f) {
+        if (f >= L.nf) continue;
+        const double all = S.rr[f] + S.xm[f] + S.mm[f] + S.sin[f] + ww[f] + T.ym[f] + T.xy[f] + T.yy[f];
+        if (!(all - all == 0.0)) st |= ST_NONFINITE;
     }
     return st;
 }

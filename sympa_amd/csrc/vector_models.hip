@@ -1,9 +1,10 @@
 // gfx950 kernels + C-ABI of the vector models (vector_math.hpp): euclidean, poincare, lorentz, sphere and
-// the four products.  G lanes per pair (forward, backward) or per row (projx, egrad2rgrad, RSGD step), G in {1, 2, ..., 64}
+// the four products.  G lanes per pair (forward, backward) or per row (projx, egrad2rgrad, RSGD step, RiemannianAdam step:
+// DESIGN.md section 20), G in {1, 2, ..., 64}
 // chosen from dims (vec_lanes): lane l owns the coordinate pairs (2c, 2c + 1), c = l, l + G, ..., so consecutive lanes read
 // consecutive 16 bytes.  The per-factor sums go through a fixed xor butterfly over the G lanes, after which every lane of the
 // pair holds the same bits and runs the scalar epilogue -- the only code that looks at the geometry (a runtime switch: the
-// instantiations are 7 values of G times three kernels).
+// instantiations are 7 values of G times four kernels).
 //
 // Every cross-lane read (the butterflies, the ballots) is executed by all 64 lanes of the wave:
 // lanes of pairs / rows past the end clamp their index to the last one, run the same arithmetic and have only their stores,
@@ -324,6 +325,149 @@ __global__ __launch_bounds__(VEC_BLOCK) void vec_row_kernel(const VecRowArgs a, 
     report_status(a.status, writer && st != 0, st);
 }
 
+struct VecAdamArgs {
+    double* x;              // the table, exp_avg and exp_avg_sq: updated in place
+    const double* g;
+    double* m;
+    double* s;
+    int64_t b;
+    double lr, beta1, beta2, eps, wd;
+    const double* pows;     // device: (beta1^t, beta2^t) of this step
+    const double* clip;     // device: squared total gradient norm, or nullptr
+    double max_norm;
+    int32_t* projected;
+    int32_t* status;
+    int dims;
+    int has_l;              // the layout has an L factor: the round for its new time coordinate is taken
+    int vec_x, vec_g, vec_m, vec_s;
+};
+
+// The RiemannianAdam row (vector_math.hpp): the lane ownership of vec_row_kernel, four rounds of sums
+// (three without an L factor), then one pass that stores the row, exp_avg and exp_avg_sq.  A lane reads and writes its own
+// coordinates only (the factor's incoming exp_avg_sq travels through a butterfly, not through memory), re-reads them from L1
+// in every round, and stores a coordinate pair after its last read of it.
+template <int G>
+__global__ __launch_bounds__(VEC_BLOCK) void vec_radam_kernel(const VecAdamArgs a, const VecLayout L) {
+    const int64_t t = (int64_t)blockIdx.x * VEC_BLOCK + threadIdx.x;
+    const int64_t p = t / G;
+    const int lane = (int)(threadIdx.x % G);
+    const bool live = p < a.b;
+    const int64_t pp = live ? p : a.b - 1;
+    const int dims = a.dims;
+    // (no __restrict__: the three tensors are read and written)
+    double* x = a.x + pp * dims;
+    const double* g = a.g + pp * dims;
+    double* m = a.m + pp * dims;
+    double* s = a.s + pp * dims;
+    const bool vx = a.vec_x != 0, vg = a.vec_g != 0, vm = a.vec_m != 0, vs = a.vec_s != 0;
+    sympa::VecAdamParams P;
+    P.lr = a.lr; P.beta1 = a.beta1; P.beta2 = a.beta2; P.eps = a.eps; P.wd = a.wd;
+    P.coef = a.clip != nullptr ? fmin(1.0, a.max_norm / (sqrt(a.clip[0]) + 1e-6)) : 1.0;
+    P.bc1 = 1.0 - a.pows[0];
+    P.bc2 = 1.0 - a.pows[1];
+
+    // round 1: xx, <x, g> (and the row's own rest, unused here)
+    sympa::VecRowSums rs;
+    sympa::vec_row_sums_zero(rs);
+    for (int i = 2 * lane; i < dims; i += 2 * G) {
+        double x0, x1, g0, g1;
+        ld2(x, i, dims, vx, x0, x1);
+        ld2(g, i, dims, vg, g0, g1);
+        sympa::vec_row_accumulate(L, i, x0, sympa::vec_row_grad(g0, x0, P.coef, P.wd), rs);
+        if (i + 1 < dims) sympa::vec_row_accumulate(L, i + 1, x1, sympa::vec_row_grad(g1, x1, P.coef, P.wd), rs);
+    }
+    for (int f = 0; f < sympa::VEC_MAX_FACTORS; ++f) { rs.xx[f] = butterfly<G>(rs.xx[f]); rs.xg[f] = butterfly<G>(rs.xg[f]); }
+    int st = sympa::vec_row_status(L, rs);
+
+    // the lane's coordinates (i, i + 1) with everything round 1 decides: r and m1
+    auto load = [&](const int i, sympa::VecAdamCoord (&c)[2]) {
+        double x0, x1, g0, g1, m0, m1, s0, s1;
+        ld2(x, i, dims, vx, x0, x1);
+        ld2(g, i, dims, vg, g0, g1);
+        ld2(m, i, dims, vm, m0, m1);
+        ld2(s, i, dims, vs, s0, s1);
+        sympa::vec_adam_coord(L, rs, P, i, x0, g0, m0, s0, c[0]);
+        sympa::vec_adam_coord(L, rs, P, (i + 1 < dims) ? i + 1 : i, x1, g1, m1, s1, c[1]);
+    };
+
+    // round 2: rr, <x, m1>, mm, the factor's incoming exp_avg_sq
+    sympa::VecAdamSums S;
+    sympa::vec_adam_sums_zero(S);
+    for (int i = 2 * lane; i < dims; i += 2 * G) {
+        sympa::VecAdamCoord c[2];
+        load(i, c);
+        sympa::vec_adam_accumulate(L, i, c[0], S);
+        if (i + 1 < dims) sympa::vec_adam_accumulate(L, i + 1, c[1], S);
+    }
+    for (int f = 0; f < sympa::VEC_MAX_FACTORS; ++f) {
+        S.rr[f] = butterfly<G>(S.rr[f]); S.xm[f] = butterfly<G>(S.xm[f]); S.mm[f] = butterfly<G>(S.mm[f]);
+        S.sin[f] = butterfly<G>(S.sin[f]);
+    }
+    sympa::VecAdamStep as;
+    double ww[sympa::VEC_MAX_FACTORS];
+    sympa::vec_adam_step(L, rs, S, P, as, ww);
+    bool moved = false;
+    sympa::VecRowStep sc;
+    sympa::vec_row_step_coef(L, ww, sc, moved);
+
+    // round 3 (wave-uniform: the layout is a kernel argument): the L factor's new time coordinate
+    double rest[sympa::VEC_MAX_FACTORS] = {0.0, 0.0};
+    if (a.has_l) {
+        for (int i = 2 * lane; i < dims; i += 2 * G) {
+            sympa::VecAdamCoord c[2];
+            load(i, c);
+            for (int k = 0; k < 2 && i + k < dims; ++k) {
+                const int f = sympa::vec_factor_of(L, i + k);
+                if (i + k != (f ? L.begin[1] : L.begin[0])) {
+                    const double z = sympa::vec_row_stage2(L, sc, i + k, c[k].x, sympa::vec_adam_stage1(L, as, P, i + k, c[k]));
+                    const double acc = sympa::d_fma(z, z, f ? rest[1] : rest[0]);
+                    if (f) rest[1] = acc; else rest[0] = acc;
+                }
+            }
+        }
+        rest[0] = butterfly<G>(rest[0]); rest[1] = butterfly<G>(rest[1]);
+    }
+
+    // round 4: the transport's inner products on the row as it will be stored
+    sympa::VecTranspSums T;
+    sympa::vec_transp_sums_zero(T);
+    for (int i = 2 * lane; i < dims; i += 2 * G) {
+        sympa::VecAdamCoord c[2];
+        load(i, c);
+        for (int k = 0; k < 2 && i + k < dims; ++k) {
+            const double z = sympa::vec_row_stage2(L, sc, i + k, c[k].x, sympa::vec_adam_stage1(L, as, P, i + k, c[k]));
+            sympa::vec_transp_accumulate(L, i + k, c[k].x, sympa::vec_row_final(L, rest, i + k, z), c[k].m1, T);
+        }
+    }
+    for (int f = 0; f < sympa::VEC_MAX_FACTORS; ++f) {
+        T.ym[f] = butterfly<G>(T.ym[f]); T.xy[f] = butterfly<G>(T.xy[f]); T.yy[f] = butterfly<G>(T.yy[f]);
+    }
+    sympa::VecTransp tc;
+    sympa::vec_transp_coef(L, rs.xx, S.xm, T, tc);
+    st |= sympa::vec_adam_status(L, S, ww, T);
+
+    for (int i = 2 * lane; i < dims; i += 2 * G) {
+        sympa::VecAdamCoord c[2];
+        load(i, c);
+        double y[2] = {0.0, 0.0}, mo[2] = {0.0, 0.0}, so[2] = {0.0, 0.0};
+        for (int k = 0; k < 2 && i + k < dims; ++k) {
+            const double z = sympa::vec_row_stage2(L, sc, i + k, c[k].x, sympa::vec_adam_stage1(L, as, P, i + k, c[k]));
+            y[k] = sympa::vec_row_final(L, rest, i + k, z);
+            mo[k] = sympa::vec_transp_coord(L, tc, i + k, c[k].x, y[k], c[k].m1);
+            so[k] = sympa::vec_adam_s1(L, as, P, i + k, c[k]);
+        }
+        if (live) {
+            st2(x, i, dims, vx, y[0], y[1]);
+            st2(m, i, dims, vm, mo[0], mo[1]);
+            st2(s, i, dims, vs, so[0], so[1]);
+        }
+    }
+    const bool writer = live && lane == 0;
+    const unsigned long long mask = __ballot((writer && moved) ? 1 : 0);
+    if (a.projected != nullptr && mask != 0ull && (threadIdx.x & 63) == 0) atomicAdd(a.projected, (int)__popcll(mask));
+    report_status(a.status, writer && st != 0, st);
+}
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 int check_dims(int dims, int model, VecLayout& L) {
@@ -401,6 +545,35 @@ int launch_rows(VecRowArgs& a, int model, void* stream) {
     if (gc != 0) return gc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     SYMPA_VEC_DISPATCH(vec_row_kernel, G, grid, s, a, L)
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail((int)e, hipGetErrorString(e));
+    return 0;
+}
+
+int launch_radam(VecAdamArgs& a, int model, void* stream) {
+    if (a.b < 0) return fail(SYMPA_ERR_BAD_ARG, "negative row count");
+    VecLayout L;
+    const int rc = check_dims(a.dims, model, L);
+    if (rc != 0) return rc;
+    if (!(a.beta1 >= 0.0 && a.beta1 < 1.0) || !(a.beta2 >= 0.0 && a.beta2 < 1.0))
+        return fail(SYMPA_ERR_BAD_ARG, "sympa_vector_radam_step: betas must be in [0, 1)");
+    if (!(a.eps > 0.0)) return fail(SYMPA_ERR_BAD_ARG, "sympa_vector_radam_step: eps_adam must be positive");
+    if (a.b == 0) return 0;
+    if (a.x == nullptr || a.g == nullptr || a.m == nullptr || a.s == nullptr || a.pows == nullptr)
+        return fail(SYMPA_ERR_BAD_ARG, "null buffer");
+    const bool even = a.dims % 2 == 0;
+    a.vec_x = (even && aligned16(a.x)) ? 1 : 0;
+    a.vec_g = (even && aligned16(a.g)) ? 1 : 0;
+    a.vec_m = (even && aligned16(a.m)) ? 1 : 0;
+    a.vec_s = (even && aligned16(a.s)) ? 1 : 0;
+    a.has_l = 0;
+    for (int f = 0; f < L.nf; ++f) a.has_l |= (L.geom[f] == sympa::VG_L) ? 1 : 0;
+    const int G = sympa::vec_lanes(a.dims);
+    unsigned grid;
+    const int gc = grid_of(a.b, G, grid);
+    if (gc != 0) return gc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    SYMPA_VEC_DISPATCH(vec_radam_kernel, G, grid, s, a, L)
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail((int)e, hipGetErrorString(e));
     return 0;
@@ -490,6 +663,17 @@ int sympa_vector_rsgd_step(double* table, const double* grad, int64_t num_rows, 
     a.x = table; a.g = grad; a.b = num_rows; a.dims = dims; a.op = sympa::VR_RSGD; a.lr = lr; a.wd = weight_decay;
     a.clip = total_sqnorm; a.max_norm = max_norm; a.projected = projected_count; a.status = status;
     return launch_rows(a, model, stream);
+}
+
+int sympa_vector_radam_step(double* table, const double* grad, double* exp_avg, double* exp_avg_sq, int64_t num_rows, int dims,
+                            int model, double lr, double beta1, double beta2, double eps_adam, double weight_decay,
+                            const double* bias_pows, const double* total_sqnorm, double max_norm, int32_t* projected_count,
+                            int32_t* status, void* stream) {
+    VecAdamArgs a{};
+    a.x = table; a.g = grad; a.m = exp_avg; a.s = exp_avg_sq; a.b = num_rows; a.dims = dims;
+    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps_adam; a.wd = weight_decay; a.pows = bias_pows;
+    a.clip = total_sqnorm; a.max_norm = max_norm; a.projected = projected_count; a.status = status;
+    return launch_radam(a, model, stream);
 }
 
 }  // extern "C"

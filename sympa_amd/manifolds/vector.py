@@ -111,6 +111,63 @@ def torch_rsgd_row(x, grad, model, lr, wd=0.0):
     return torch_retr(x, -lr * torch_egrad2rgrad(x, g, model), model)
 
 
+def torch_component_inner(x, u, v, model):
+    """geoopt's component_inner per factor: E: u_i v_i per coordinate; P: (2 / (1 - xx))^2 <u, v>, S: <u, v>,
+    L: <u, v>_L, one value per factor held in every coordinate of the factor."""
+    out = torch.empty_like(u)
+    for g, s in _factor_slices(model, x.shape[-1]):
+        xs, us, vs = x[..., s], u[..., s], v[..., s]
+        if g == "E":
+            out[..., s] = us * vs
+            continue
+        if g == "L":
+            val = (_lorentz_sign(xs) * us * vs).sum(-1, keepdim=True)
+        else:
+            val = (us * vs).sum(-1, keepdim=True)
+        if g == "P":
+            val = val * (2.0 / (1.0 - (xs * xs).sum(-1, keepdim=True))) ** 2
+        out[..., s] = val.expand_as(us)
+    return out
+
+
+def torch_transp(x, y, v, model):
+    """Parallel transport of v from x to y per factor, in forms that are the identity at y = x without a 0 / 0 (section 20):
+    E: v;  S: v - <y, v> y;  L: v + <y, v>_L / (2 + dd_L / 2) (x + y), dd_L = <x - y, x - y>_L;  P: (1 - yy) / (1 - xx) gyr[y, -x] v."""
+    out = torch.empty_like(v)
+    for g, s in _factor_slices(model, x.shape[-1]):
+        xs, ys, vs = x[..., s], y[..., s], v[..., s]
+        if g == "E":
+            out[..., s] = vs
+        elif g == "S":
+            out[..., s] = vs - (ys * vs).sum(-1, keepdim=True) * ys
+        elif g == "L":
+            j = _lorentz_sign(xs)
+            w = xs - ys
+            den = 2.0 + 0.5 * (j * w * w).sum(-1, keepdim=True)
+            out[..., s] = vs + (j * ys * vs).sum(-1, keepdim=True) / den * (xs + ys)
+        else:
+            # gyr[a, b] v = v + 2 (A a + B b) / D with a = y, b = -x
+            aw, bw = (ys * vs).sum(-1, keepdim=True), -(xs * vs).sum(-1, keepdim=True)
+            ab = -(xs * ys).sum(-1, keepdim=True)
+            aa, bb = (ys * ys).sum(-1, keepdim=True), (xs * xs).sum(-1, keepdim=True)
+            A = -aw * bb + bw + 2.0 * ab * bw
+            B = -bw * aa - aw
+            D = 1.0 + 2.0 * ab + aa * bb
+            out[..., s] = (1.0 - aa) / (1.0 - bb) * (vs + 2.0 * (A * ys - B * xs) / D)
+    return out
+
+
+def torch_radam_row(x, grad, exp_avg, exp_avg_sq, pows, model, lr, betas=(0.9, 0.999), eps=1e-8, wd=0.0):
+    """The RiemannianAdam row of section 20 in torch ops -> (new rows, exp_avg, exp_avg_sq); pows = (beta1^t, beta2^t)."""
+    g = grad + wd * x
+    r = torch_egrad2rgrad(x, g, model)
+    m1 = betas[0] * exp_avg + (1.0 - betas[0]) * r
+    s1 = betas[1] * exp_avg_sq + (1.0 - betas[1]) * torch_component_inner(x, r, r, model).clamp_min(0.0)
+    u = -lr * (m1 / (1.0 - pows[0])) / ((s1 / (1.0 - pows[1])).sqrt() + eps)
+    y = torch_retr(x, u, model)
+    return y, torch_transp(x, y, m1, model), s1
+
+
 class VectorManifold(Manifold):
     """Common part of the five classes: `model_name` selects the factors; everything on the device is one kernel."""
     ndim = 1
@@ -182,7 +239,27 @@ class VectorManifold(Manifold):
         return torch_retr(x, u, self.model_name)
 
     def transp(self, x, y, v):
-        raise NotImplementedError("the vector models' parallel transports are not built (RiemannianAdam needs them): use rsgd")
+        """Parallel transport of the tangent vector v from x to y (plain torch, any device; the optimiser's is inside the fused
+        sympa_vector_radam_step)."""
+        ops.vector_check_dims(self.model_name, x.shape[-1])
+        return torch_transp(x, y, v, self.model_name)
+
+    def component_inner(self, x, u, v=None):
+        """geoopt's component_inner, in the shape of x: what RiemannianAdam's second moment accumulates."""
+        ops.vector_check_dims(self.model_name, x.shape[-1])
+        return torch_component_inner(x, u, u if v is None else v, self.model_name)
+
+    def inner(self, x, u, v=None, keepdim=False):
+        """The Riemannian inner product <u, v>_x: the sum over the factors (E: the plain dot product)."""
+        ops.vector_check_dims(self.model_name, x.shape[-1])
+        v = u if v is None else v
+        total = None
+        for g, s in _factor_slices(self.model_name, x.shape[-1]):
+            ci = torch_component_inner(x[..., s], u[..., s], v[..., s], {"E": "euclidean", "P": "poincare", "L": "lorentz",
+                                                                         "S": "sphere"}[g])
+            val = ci.sum(-1, keepdim=True) if g == "E" else ci[..., :1]
+            total = val if total is None else total + val
+        return total if keepdim else total.squeeze(-1)
 
     def projx(self, x):
         if x.is_cuda:

@@ -1709,6 +1709,32 @@ def vector_rsgd_step_(table, grad, model, lr, weight_decay=0.0, counter=None, cl
     return table
 
 
+def vector_radam_step_(table, grad, exp_avg, exp_avg_sq, bias_pows, model, lr, betas=(0.9, 0.999), eps_adam=1e-8, weight_decay=0.0,
+                       counter=None, clip_sqnorm=None, max_norm=None):
+    """In-place geoopt RiemannianAdam step over a vector model's table as ONE kernel (C-ABI sympa_vector_radam_step): table / grad
+    / exp_avg / exp_avg_sq [N, dims] (exp_avg_sq holds a P, S or L factor's value in every coordinate of the factor), bias_pows =
+    device tensor (beta1^t, beta2^t) of this step.  exp_avg is parallel-transported to the new point."""
+    lib = _lib.load()
+    _need_gpu(table, "table")
+    grad = _vec_rows(grad.detach(), "grad")
+    for name, t, shape in (("table", table, grad.shape), ("exp_avg", exp_avg, grad.shape), ("exp_avg_sq", exp_avg_sq, grad.shape),
+                           ("bias_pows", bias_pows, (2,))):
+        if t.dtype != torch.float64 or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != table.device:
+            raise ValueError(f"{name} must be a contiguous float64 tensor of shape {tuple(shape)} on {table.device}, got "
+                             f"{tuple(t.shape)} {t.dtype} on {t.device}")
+    vector_check_dims(model, table.shape[1])
+    st = _status_buf(table.device)
+    with torch.cuda.device(table.device):
+        rc = lib.sympa_vector_radam_step(table.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), table.shape[0],
+                                         table.shape[1], VECTOR_MODEL_IDS[model], float(lr), float(betas[0]), float(betas[1]),
+                                         float(eps_adam), float(weight_decay), bias_pows.data_ptr(),
+                                         None if clip_sqnorm is None else clip_sqnorm.data_ptr(),
+                                         float(max_norm) if max_norm is not None else 0.0,
+                                         None if counter is None else counter.data_ptr(), st.data_ptr(), _stream())
+    _lib.check(rc)
+    return table
+
+
 # ---------------------------------------------------------------------------------------------------
 # Mean average precision (C-ABI sympa_map_rows; reference sympa/metrics.py:25-63, runner.py:137-154)
 # ---------------------------------------------------------------------------------------------------

@@ -103,7 +103,9 @@ class RiemannianAdam(torch.optim.Optimizer):
         x  <- retr(x, -lr * (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps));   m is transported by the identity
     (SiegelManifold.transp returns the vector unchanged, siegel_manifold.py:142-154).  egrad2rgrad, inner and retr
     (= projx(x + u)) are HIP kernels over the table rows; the moment updates are elementwise torch ops on the device.
-    Parameters without a manifold get the ordinary Adam update.  amsgrad is not built.
+    A table of a vector model (euclidean, poincare, lorentz, sphere, the products) on the device takes the same step per factor
+    as ONE kernel over its rows (sympa_vector_radam_step): exp_avg_sq has the table's shape, and exp_avg is
+    parallel-transported to the new point.  Parameters without a manifold get the ordinary Adam update.  amsgrad is not built.
 
     The powers b1^t, b2^t live in two device words per parameter and are advanced by the step itself, so nothing the step
     computes depends on host state that changes from call to call: the step can be captured in a hipGraph
@@ -192,12 +194,20 @@ class RiemannianAdam(torch.optim.Optimizer):
                     ops.table_changed(p)       # (see RiemannianSGD.step)
                 if isinstance(manifold, SymmetricPositiveDefinite):
                     raise NotImplementedError("RiemannianAdam on the spd model needs geoopt's parallel transport: use rsgd")
-                if isinstance(manifold, VectorManifold):
-                    raise NotImplementedError("RiemannianAdam on the vector models needs their parallel transports, which are not "
-                                              "built: use rsgd")
+                if isinstance(manifold, VectorManifold) and not p.is_cuda:
+                    raise NotImplementedError("RiemannianAdam on a vector model's table is one HIP kernel over the table "
+                                              "(sympa_vector_radam_step) and is not built for a table on the host: move the model "
+                                              "to the device, or use rsgd")
                 state = self._init_param_state(p, (b1, b2), group["step"] - 1)
                 m, v = state["exp_avg"], state["exp_avg_sq"]
                 pows = state["bias_pows"].mul_(state["betas"])      # (b1^t, b2^t), t = steps this parameter has taken: one launch
+                if isinstance(manifold, VectorManifold):
+                    if p.dtype != torch.float64:
+                        raise TypeError("a vector model's table must be float64 (config.py:17-18)")
+                    # the whole row update in one kernel: moments, retraction, the parallel transport of exp_avg to the new point
+                    ops.vector_radam_step_(p.data, p.grad, m, v, state["bias_pows"], manifold.model_name, lr, (b1, b2), eps, wd,
+                                           counter=manifold.projected_counter(p.device))
+                    continue
                 if siegel and p.shape[2] <= ops.RADAM_FUSED_MAX_DIMS and p.data.is_contiguous() and p.dtype == torch.float64:
                     # the whole row update in one kernel (C-ABI sympa_radam_step); the powers were advanced just above
                     ops.radam_step_(p.data, p.grad, m, v, state["bias_pows"], manifold.model_name, lr, (b1, b2), eps, wd,

@@ -7,6 +7,7 @@ rewrite of them: SURVEY 8f): graph -> triplets -> Model -> fused training step -
     python tools/train_siegel.py --edges data/usca312/usca312.edges --dims 3 --epochs 50
     python tools/train_siegel.py --graph grid3d-125 --subsample 0.25 --scale_triplets
     python tools/train_siegel.py --graph product-cartesian-45500 --dims 8 --sampled-pairs 1048576 --batch_size 262144 --subsample 0.01
+    python tools/train_siegel.py --graph grid3d-125 --manifold poincare --optim radam --dims 4
 
 Per batch it runs exactly two kernels: sympa_model_loss_backward (forward + AverageDistortionLoss + backward +
 scatter, runner.py:101-105) and sympa_rsgd_step (geoopt RiemannianSGD, train.py:66-68), plus the gradient clip
@@ -129,7 +130,8 @@ def train(args, log=print):
     graphed = GraphedTrainStep(model, opt, batch, args.max_grad_norm, dev,
                                deterministic=True if args.deterministic else None, accumulate_loss=True) \
         if (world == 1 and args.graph_step and args.grad_exchange == "none" and args.manifold not in ops.VECTOR_MODEL_IDS) else None
-    # (the vector models train through the classic loop below: fused loss + backward rows + scatter, clip, RiemannianSGD.step)
+    # (the vector models train through the classic loop below: fused loss + backward rows + scatter, clip, then the optimiser's
+    # step -- RiemannianSGD or, with --optim radam, RiemannianAdam: one kernel over the table either way)
     if args.manifold in ops.VECTOR_MODEL_IDS and (world > 1 or args.grad_exchange != "none"):
         raise SystemExit(f"--manifold {args.manifold}: the gradient exchange is not wired to the vector models (single GPU only)")
     # (RiemannianAdam keeps its powers b^t in device words, so its step is captured too -- as the same two kernels where the

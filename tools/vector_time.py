@@ -15,7 +15,12 @@ dims 272 in the Infinity Cache (256 MB), so gathered rows need not come from HBM
 where it does.  Kernel and torch results are compared before anything is timed.  Times are host clocks around work that ends in a
 device synchronise, warm, median of 5, the forms alternating.  Recorded numbers only: nothing here is a threshold.
 
-    python tools/vector_time.py [--out profiles/vector_time.json]"""
+`--radam` measures the RiemannianAdam step instead (sympa_vector_radam_step, one launch, against torch_radam_row of
+sympa_amd/manifolds/vector.py on the same tensors) with its bytes roof of 7 dims 8 bytes per row (read x, g, m, s; write x, m, s),
+and writes profiles/vector_radam_time.json; the table says where the kernel loses to torch.
+
+    python tools/vector_time.py [--out profiles/vector_time.json]
+    python tools/vector_time.py --radam [--out profiles/vector_radam_time.json]"""
 import argparse
 import json
 import os
@@ -145,10 +150,68 @@ def measure(model, dims, log):
     return out
 
 
+def measure_radam(model, dims, log):
+    """The RiemannianAdam step over the same table (sympa_vector_radam_step, one launch) against torch_radam_row on the same
+    tensors.  Bytes roof: a row reads x, g, m, s and writes x, m, s: 7 dims 8 bytes."""
+    import torch
+    from sympa_amd import ops
+    from sympa_amd.manifolds import vector as mv
+    from sympa_amd.manifolds.base import ManifoldParameter
+    from sympa_amd.optim import RiemannianAdam
+    dev = torch.device("cuda:0")
+    lr, betas, eps = 1e-3, (0.9, 0.999), 1e-7
+    table = spread_table(model, dims, dev)
+    p = ManifoldParameter(table.clone(), manifold=mv.get_vector_manifold(model, dims))
+    g = torch.Generator().manual_seed(2)
+    grad = (torch.randn(ROWS, dims, generator=g, dtype=torch.float64) / dims ** 0.5).to(dev)
+    p.grad = grad
+    opt = RiemannianAdam([p], lr=lr, betas=betas, eps=eps)
+    # results first: three steps of the optimiser against three torch rows (the warm-up too)
+    x, m, s = table.clone(), torch.zeros_like(table), torch.zeros_like(table)
+    for t in (1, 2, 3):
+        opt.step()
+        x, m, s = mv.torch_radam_row(x, grad, m, s, (betas[0] ** t, betas[1] ** t), model, lr, betas, eps)
+    st = opt.state[p]
+    errs = {"x": float((p.data - x).abs().max() / x.abs().max()), "exp_avg": float((st["exp_avg"] - m).abs().max() / m.abs().max()),
+            "exp_avg_sq": float((st["exp_avg_sq"] - s).abs().max() / s.abs().max())}
+    assert ops.check_status(dev) == (0, 0)
+    assert max(errs.values()) < 1e-10, errs
+    pows = torch.tensor([betas[0] ** 4, betas[1] ** 4], dtype=torch.float64, device=dev)
+    state = [x, m, s]
+
+    def radam():
+        opt.step()                                     # (the table drifts by lr = 1e-3 steps: harmless)
+
+    def torch_radam():
+        with torch.no_grad():
+            state[0], state[1], state[2] = mv.torch_radam_row(state[0], grad, state[1], state[2], pows, model, lr, betas, eps)
+
+    passes = {"radam": radam, "torch_radam": torch_radam}
+    for run in passes.values():
+        run()
+    times = {k: [] for k in passes}
+    for _ in range(5):
+        for k, run in passes.items():
+            times[k].append(once_ms(run))
+    ms = {k: {"median_ms": sorted(v)[len(v) // 2], "all_ms": v} for k, v in times.items()}
+    roof_ms = ROWS * 7 * dims * 8 / HBM_BYTES_PER_S * 1e3
+    out = {"rows": ROWS, "dims": dims, "lanes_per_row": min(64, 1 << max(0, (dims - 1).bit_length() - 2)),
+           "table_megabytes": round(ROWS * dims * 8 / 1e6, 1), "max_relative_difference_kernel_torch_after_3_steps": errs,
+           "passes": ms, "torch_over_kernel": round(ms["torch_radam"]["median_ms"] / ms["radam"]["median_ms"], 2),
+           "kernel_loses_to_torch": ms["radam"]["median_ms"] > ms["torch_radam"]["median_ms"],
+           "bytes_roof_ms": round(roof_ms, 4), "radam_over_roof": round(ms["radam"]["median_ms"] / roof_ms, 2)}
+    log(f"{model} dims {dims} radam: {json.dumps(out)}")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "vector_time.json"))
+    ap.add_argument("--radam", action="store_true",
+                    help="measure the RiemannianAdam step alone (default --out: profiles/vector_radam_time.json)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "vector_radam_time.json" if args.radam else "vector_time.json")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("vector_time.py measures on a GPU and found none")
@@ -159,7 +222,7 @@ def main():
               "timing": "host clock around a pass that ends in a device synchronise, warm, median of 5, forms alternating"}
     for model in MODELS:
         for dims in DIMS:
-            result[f"{model}-{dims}"] = measure(model, dims, log)
+            result[f"{model}-{dims}"] = measure_radam(model, dims, log) if args.radam else measure(model, dims, log)
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1, sort_keys=True)
         f.write("\n")
