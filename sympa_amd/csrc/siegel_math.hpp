@@ -383,24 +383,41 @@ SYMPA_UNROLL
 // scalar on the eight results: 1 + 16 + 16 + 8 = 41 instructions where two separate rotations spend 2 * 24 = 48
 // (each has a `c * x` in front of every fma pair).  s / (a c) is the product the diagonal shift t a forms anyway.
 // n = 3 has one row outside each pivot, nothing to share: it keeps the rotation by rotation form, cyclic by rows.
+//
+// The round never needs the cosine of ONE rotation: c_A and c_B enter through the product c_A c_B (the scalar above) and
+// through 1 / c^2 (in s / (a c) = sgn(delta) / (r c^2)).  So the round takes one reciprocal square root per rotation (for r)
+// and ONE for both cosines, three where two separate rotations take four.  Per rotation X, in halves of delta (scalings by
+// two are exact, these are the values of the formulas above):
+//   eta = |delta| / 2 (+ 0.5e-150),   rho = 1 / sqrt(eta^2 + a^2) = 2 / r,   C = 1 + eta rho = 1 + |delta| / r = 2 c^2  in [1, 2].
+// Jointly:  P = C_A C_B = 4 c_A^2 c_B^2  in [1, 4] whatever the scale of H (no range problem for the seed),  w = 1 / sqrt(P):
+//   c_A c_B = sqrt(P) / 2 = (P / 2) w,     1 / C_A = C_B / P = w^2 C_B,     1 / C_B = w^2 C_A,
+//   s / (a c) of X = sgn(delta) / (r c^2) = sgn(delta) (2 / r) / (2 c^2) = sgn(delta_X) rho_X / C_X.
+// The two rho keep a reciprocal square root each: their arguments scale with ||H||^2 (1e-300 for identical points), a product
+// of the two would leave the range.
 // ---------------------------------------------------------------------------------------------
-// Parameters of the rotation on pivot (p,q):  c = cos,  tau = (tr, ti),  ua2 = t |beta| (the diagonal shift).
-template <int N>
-SYMPA_HD void jacobi_angle(const Herm<N>& h, const int p, const int q, double& c, double& tr, double& ti, double& ua2) {
-    const double br = h.re[p][q], bi = h.im[p][q];
-    const double a2 = d_fma(br, br, bi * bi);
-    const double delta = h.d[q] - h.d[p];
-    // |delta| + 1e-150 keeps r2 > 0 (and gives c = 1, tau = 0) when beta = delta = 0
-    const double ad = fabs(delta) + 1e-150;
-    const double qr = d_rsqrt(d_fma(ad, ad, 4.0 * a2));      // 1 / r,  r = sqrt(delta^2 + 4 a^2)
-    const double c2 = d_fma(0.5 * ad, qr, 0.5);                // cos^2 = (1 + |delta|/r) / 2
-    const double ic = d_rsqrt(c2);
-    c = c2 * ic;
-    const double cu = copysign(qr, delta) * ic;                // s / a, signed
-    const double uc = cu * ic;                                 // s / (a c)
-    ua2 = uc * a2;                                             // t * |beta|
-    tr = uc * br;
-    ti = uc * bi;
+// Parameters of the two rotations of a round, A on pivot (p,q) and B on (r,s):  cc = c_A c_B,  tau_A = (ar, ai),
+// tau_B = (br, bi),  ua, ub = t |beta| of each (the diagonal shifts).
+SYMPA_HD void jacobi_round_angles(const Herm<4>& h, const int p, const int q, const int r, const int s, double& cc,
+                                  double& ar, double& ai, double& ua, double& br, double& bi, double& ub) {
+    const double xr = h.re[p][q], xi = h.im[p][q], yr = h.re[r][s], yi = h.im[r][s];
+    const double a2a = d_fma(xr, xr, xi * xi), a2b = d_fma(yr, yr, yi * yi);
+    const double da = h.d[q] - h.d[p], db = h.d[s] - h.d[r];
+    // |delta| / 2 + 0.5e-150 keeps eta^2 + a^2 > 0 (and gives C = 2, tau = 0) when beta = delta = 0
+    const double ea = d_fma(fabs(da), 0.5, 0.5e-150), eb = d_fma(fabs(db), 0.5, 0.5e-150);
+    const double ra = d_rsqrt(d_fma(ea, ea, a2a)), rb = d_rsqrt(d_fma(eb, eb, a2b));   // 2 / r
+    const double c2a = d_fma(ea, ra, 1.0), c2b = d_fma(eb, rb, 1.0);                   // 2 cos^2
+    const double pc = c2a * c2b;
+    const double w = d_rsqrt(pc);                                                      // 1 / (2 c_A c_B)
+    cc = (0.5 * pc) * w;
+    const double w2 = w * w;
+    const double uca = copysign(ra, da) * (w2 * c2b);                                  // s / (a c), signed
+    const double ucb = copysign(rb, db) * (w2 * c2a);
+    ua = uca * a2a;                                                                    // t * |beta|
+    ar = uca * xr;
+    ai = uca * xi;
+    ub = ucb * a2b;
+    br = ucb * yr;
+    bi = ucb * yi;
 }
 
 template <int N>
@@ -459,9 +476,8 @@ enum RoundZeros : int { ROUND_FULL = 0, ROUND_DIAG = 1, ROUND_ANTI = 2 };
 
 template <int ZEROS>
 SYMPA_HD void jacobi_round(Herm<4>& h, const int p, const int q, const int r, const int s) {
-    double ca, ar, ai, ua, cb, br, bi, ub;
-    jacobi_angle<4>(h, p, q, ca, ar, ai, ua);      // neither rotation changes what the other one's parameters read
-    jacobi_angle<4>(h, r, s, cb, br, bi, ub);
+    double cc, ar, ai, ua, br, bi, ub;
+    jacobi_round_angles(h, p, q, r, s, cc, ar, ai, ua, br, bi, ub);   // neither rotation changes what the other one's parameters read
     h.d[p] -= ua;
     h.d[q] += ua;
     h.d[r] -= ub;
@@ -470,7 +486,6 @@ SYMPA_HD void jacobi_round(Herm<4>& h, const int p, const int q, const int r, co
     h.im[p][q] = 0.0;
     h.re[r][s] = 0.0;
     h.im[r][s] = 0.0;
-    const double cc = ca * cb;
     const int row[2] = {p, q}, col[2] = {r, s};
     double mr[2][2], mi[2][2];
 SYMPA_UNROLL
@@ -569,12 +584,14 @@ SYMPA_UNROLL
 // one reciprocal and no square root; the O(t^4) is the order the finishing sweep drops anyway (t^2 <= 1e-3 under the certificate;
 // the form with r and 1 / c^2 = 2 - c^2 it replaces dropped the same order).  A pivot the certificate passed as negligible
 // (a^2 <= 1e-24 ||diag||^2) may have any t: its shift is at most a <= 1e-12 ||diag|| in either form.  |delta| + 1e-150 keeps the
-// denominator positive when a = delta = 0.
+// denominator positive when a = delta = 0.  The product is formed as a^2 * (delta / (delta^2 + a^2)): the quotient is of the order
+// 1 / ||H|| and the shift of the order ||H||, where (a^2 * delta) first is a cubic in ||H|| that leaves the fp64 range from
+// ||H|| ~ 1e103 (NaN eigenvalues) and underflows to a dropped shift below ~1e-103; the rounds have no such limit.
 template <int N>
 SYMPA_HD void jacobi_diag_update(Herm<N>& h, const int p, const int q, const double a2) {
     const double delta = h.d[q] - h.d[p];
     const double ad = fabs(delta) + 1e-150;
-    const double ua2 = (a2 * delta) * d_rcp(d_fma(ad, ad, a2));
+    const double ua2 = a2 * (delta * d_rcp(d_fma(ad, ad, a2)));
     h.d[p] -= ua2;
     h.d[q] += ua2;
 }
