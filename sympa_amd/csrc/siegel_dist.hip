@@ -183,14 +183,18 @@ int launch_multi(const double* table, int64_t num_rows, int n, const int64_t* co
     m.c.status = status;
     m.c.metric = metric;
     m.c.flags = flags;
-    uint64_t blocks = 0;
+    uint64_t blocks = 0, per_batch = 0;
+    bool uniform = true;            // every non-empty batch has the same number of blocks
     int k = 0;
     const int fb = fwd_block(n);
     for (int i = 0; i < cnt; ++i) {
         if (b[i] < 0) return fail(SYMPA_ERR_BAD_ARG, "negative batch size");
         if (b[i] == 0) continue;
         if (triplets[i] == nullptr || out[i] == nullptr) return fail(SYMPA_ERR_BAD_ARG, "null buffer");
-        blocks += (uint64_t)((b[i] + fb - 1) / fb);
+        const uint64_t mine = (uint64_t)((b[i] + fb - 1) / fb);
+        if (k == 0) per_batch = mine;
+        uniform = uniform && mine == per_batch;
+        blocks += mine;
         if (blocks > 0x7fffffffull) return fail(SYMPA_ERR_BAD_ARG, "batches too large for one launch");
         m.trip[k] = triplets[i];
         m.out[k] = out[i];
@@ -199,8 +203,9 @@ int launch_multi(const double* table, int64_t num_rows, int n, const int64_t* co
         ++k;
     }
     if (k == 0) return 0;
-    for (int i = k; i < SYMPA_MAX_FUSED_BATCHES; ++i) m.blk_end[i] = (unsigned)blocks;   // the search never lands there
+    for (int i = k; i < SYMPA_MAX_FUSED_BATCHES; ++i) m.blk_end[i] = (unsigned)blocks;   // above every block number: never counted
     m.num_batches = k;
+    multi_uniform_blocks(m, uniform ? per_batch : 0);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (model == SYMPA_MODEL_DUAL) {
         if (n >= 1 && n <= SYMPA_MAX_DIMS) return launch_multi_dual(m, (unsigned)blocks, n, s);
@@ -262,6 +267,16 @@ int sympa_set_instance_fallback(int family, int model, int n, int on) {
 }
 
 int sympa_get_instance_fallback(int family, int model, int n) { return sympa_hip::instance_fallback(family, model, n) ? 1 : 0; }
+
+#ifdef SYMPA_HEAD_TIMELINE
+// profile build only (tools/head_timeline.py): the buffer the next fused launches stamp, 8 words per block; nullptr switches it off
+int sympa_head_timeline_buffer(void* buf, unsigned blocks) {
+    unsigned long long* p = reinterpret_cast<unsigned long long*>(buf);
+    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(sympa_hip::g_head_timeline), &p, sizeof(p));
+    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(sympa_hip::g_head_timeline_blocks), &blocks, sizeof(blocks));
+    return e == hipSuccess ? 0 : sympa_hip::fail((int)e, hipGetErrorString(e));
+}
+#endif
 
 const char* sympa_version(void) { return "sympa_hip 0.1.0 (gfx950)"; }
 const char* sympa_last_error(void) { return sympa_hip::last_error_buffer(); }

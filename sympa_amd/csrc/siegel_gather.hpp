@@ -133,25 +133,26 @@ __device__ __forceinline__ int group_bcast(const int v) {
 
 template <int N, int J>
 struct DmaIssue {
-    static __device__ __forceinline__ void run(const double* __restrict__ base, const int row, const int c,
+    // rowoff = this lane's row index times the row size, c16 = 16 x this lane's chunk: both formed once per endpoint, so the
+    // address of an instruction is ONE VALU instruction, the broadcast folded into the OR as its DPP operand
+    static __device__ __forceinline__ void run(const double* __restrict__ base, const unsigned rowoff, const unsigned c16,
                                                const unsigned side) {
         constexpr int C = DmaTile<N>::C;
-        const int rr = group_bcast<C, J>(row);
         // 32-bit byte offset from the (wave-uniform) table base: scalar base + vector offset addressing, no 64-bit
         // address arithmetic per instruction (tables of n <= 4 are limited to 4 GiB, checked on the host)
-        const unsigned off = (unsigned)rr * (unsigned)(16 * N * N) + (unsigned)(16 * c);
+        const unsigned off = (unsigned)group_bcast<C, J>((int)rowoff) | c16;
         const char* src = reinterpret_cast<const char*>(base) + off;
         __builtin_amdgcn_global_load_lds((glb_ptr_t)src, lds_dest_at(side + (unsigned)(J * DmaTile<N>::INSTR_SLOTS) * 16u), 16, 0, 0);
-        if constexpr (J + 1 < C) DmaIssue<N, J + 1>::run(base, row, c, side);
+        if constexpr (J + 1 < C) DmaIssue<N, J + 1>::run(base, rowoff, c16, side);
     }
 };
 
 template <int N>
 __device__ __forceinline__ void dma_issue(const double* __restrict__ base, const int row, v2d* __restrict__ side) {
     constexpr int C = DmaTile<N>::C;
-    const int lane = threadIdx.x & 63;
-    const int c = lane % C;
-    DmaIssue<N, 0>::run(base, row, c, lds_offset_uniform(side));
+    static_assert((C & (C - 1)) == 0, "row size a power of two: row offset | chunk offset");
+    const unsigned lane = threadIdx.x & 63;
+    DmaIssue<N, 0>::run(base, (unsigned)row * (unsigned)(16 * C), (lane % C) * 16u, lds_offset_uniform(side));
 }
 
 template <int N>
@@ -227,13 +228,12 @@ __device__ __forceinline__ void gather_pair_dma_low(const double* __restrict__ b
 // against 10.84 for the one-endpoint-at-a-time form on 2 streams.
 template <int P, int J>
 struct DmaIssuePass4 {
-    static __device__ __forceinline__ void run(const double* __restrict__ base, const int row, const int c,
+    static __device__ __forceinline__ void run(const double* __restrict__ base, const unsigned rowoff, const unsigned c16,
                                                const unsigned buf) {
-        const int rr = group_bcast<16, 4 * P + J>(row);
-        const unsigned off = (unsigned)rr * 256u + (unsigned)(16 * c);
+        const unsigned off = (unsigned)group_bcast<16, 4 * P + J>((int)rowoff) | c16;   // (as in DmaIssue)
         const char* src = reinterpret_cast<const char*>(base) + off;
         __builtin_amdgcn_global_load_lds((glb_ptr_t)src, lds_dest_at(buf + (unsigned)(J * DmaTile<4>::INSTR_SLOTS) * 16u), 16, 0, 0);
-        if constexpr (J + 1 < 4) DmaIssuePass4<P, J + 1>::run(base, row, c, buf);
+        if constexpr (J + 1 < 4) DmaIssuePass4<P, J + 1>::run(base, rowoff, c16, buf);
     }
 };
 
@@ -262,9 +262,9 @@ constexpr int PASS4_BUF_SLOTS = 4 * 65;
 constexpr int PASS4_WAVE_SLOTS = 2 * PASS4_BUF_SLOTS;
 
 template <int S>
-__device__ __forceinline__ void pass4_step(const double* __restrict__ base1, const int row1,
-                                           const double* __restrict__ base2, const int row2, v2d* __restrict__ buf0,
-                                           v2d* __restrict__ buf1, const int c, sympa::CMat<4>& z1, sympa::CMat<4>& z2) {
+__device__ __forceinline__ void pass4_step(const double* __restrict__ base1, const unsigned row1,
+                                           const double* __restrict__ base2, const unsigned row2, v2d* __restrict__ buf0,
+                                           v2d* __restrict__ buf1, const unsigned c, sympa::CMat<4>& z1, sympa::CMat<4>& z2) {
     v2d* cur = (S & 1) ? buf1 : buf0;
     v2d* nxt = (S & 1) ? buf0 : buf1;
     if constexpr (S + 1 < 8) {
@@ -285,13 +285,12 @@ __device__ __forceinline__ void pass4_step(const double* __restrict__ base1, con
 __device__ __forceinline__ void gather_pair_pass4(const double* __restrict__ base1, const int row1,
                                                   const double* __restrict__ base2, const int row2,
                                                   v2d* __restrict__ tile, sympa::CMat<4>& z1, sympa::CMat<4>& z2) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { z1.re[i][j] = 0.0; z1.im[i][j] = 0.0; z2.re[i][j] = 0.0; z2.im[i][j] = 0.0; }
-    const int c = (threadIdx.x & 63) & 15;
-    DmaIssuePass4<0, 0>::run(base1, row1, c, lds_offset_uniform(tile));
-    pass4_step<0>(base1, row1, base2, row2, tile, tile + PASS4_BUF_SLOTS, c, z1, z2);
+    // z1, z2 need no initial value: every lane belongs to exactly one of the four lane groups and pass4_read of its group
+    // writes all of both matrices before anything reads them
+    const unsigned c16 = (threadIdx.x & 15u) * 16u;
+    const unsigned off1 = (unsigned)row1 * 256u, off2 = (unsigned)row2 * 256u;
+    DmaIssuePass4<0, 0>::run(base1, off1, c16, lds_offset_uniform(tile));
+    pass4_step<0>(base1, off1, base2, off2, tile, tile + PASS4_BUF_SLOTS, c16, z1, z2);
 }
 
 // Both endpoints: all global loads are in flight before the first transpose starts.
