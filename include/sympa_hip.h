@@ -122,7 +122,7 @@ int sympa_max_dims(void);
 #define SYMPA_FAMILY_SIEGEL_TABLE 2 /* sympa_egrad2rgrad / sympa_projx / sympa_rsgd_step* / sympa_tangent_sqnorm, n = 7..16 */
 #define SYMPA_FAMILY_SPD_FWD 3      /* sympa_spd_dist_fwd / sympa_spd_model_forward, n = 6..16 */
 #define SYMPA_FAMILY_SPD_BWD 4      /* sympa_spd_backward_rows / sympa_spd_loss_backward, n = 3..16 */
-#define SYMPA_FAMILY_SPD_TABLE 5    /* sympa_spd_egrad2rgrad / sympa_spd_rsgd_step, n = 3..16 */
+#define SYMPA_FAMILY_SPD_TABLE 5    /* sympa_spd_egrad2rgrad / sympa_spd_rsgd_step / sympa_spd_radam_step, n = 3..16 */
 #define SYMPA_NUM_FAMILIES 6
 int sympa_set_instance_fallback(int family, int model, int n, int on);
 int sympa_get_instance_fallback(int family, int model, int n);
@@ -519,6 +519,19 @@ int sympa_spd_egrad2rgrad(const double* x, const double* u, int64_t b, int n, do
 int sympa_spd_projx(const double* x, int64_t b, int n, double* out, int32_t* projected_count, int32_t* status, void* stream);
 int sympa_spd_rsgd_step(double* table, const double* grad, int64_t num_rows, int n, double lr, double weight_decay,
                         const double* total_sqnorm, double max_norm, int32_t* status, void* stream);
+/* One geoopt.optim.RiemannianAdam step (train.py:69-70, `--optim radam`) over the spd table in place, as one launch
+ * (parity unpinned with respect to geoopt like every spd entry):
+ *     S = coef sym(grad) + weight_decay x,  r = x S x,  I = tr(x^-1 r x^-1 r),
+ *     m1 = beta1 m + (1 - beta1) r,  s1 = beta2 s + (1 - beta2) I,
+ *     u = -lr / (1 - beta1^t) / (sqrt(s1 / (1 - beta2^t)) + eps_adam) m1,   x <- retr(x, u) (sympa_spd_rsgd_step's),
+ *     exp_avg <- the affine-invariant parallel transport of m1 along the geodesic to the new point,  exp_avg_sq <- s1.
+ * exp_avg: [num_rows, n, n] (read as sym(.)); exp_avg_sq: [num_rows], one value per point.  bias_pows: device pair
+ * (beta1^t, beta2^t) of this step, as for sympa_radam_step; total_sqnorm / max_norm: the folded clip, as for sympa_spd_rsgd_step.
+ * SYMPA_ERR_BAD_ARG: a null table, grad, exp_avg, exp_avg_sq or bias_pows, a beta outside [0, 1), eps_adam <= 0, total_sqnorm
+ * with max_norm <= 0;  SYMPA_ERR_UNSUPPORTED_DIMS: n outside [1, 16].  A row that does not factor raises SYMPA_ST_NOT_PD. */
+int sympa_spd_radam_step(double* table, const double* grad, double* exp_avg, double* exp_avg_sq, int64_t num_rows, int n,
+                         double lr, double beta1, double beta2, double eps_adam, double weight_decay, const double* bias_pows,
+                         const double* total_sqnorm, double max_norm, int32_t* status, void* stream);
 
 /* ---- Vector models (manifolds "euclidean", "poincare", "lorentz", "sphere", "prod-hysph", "prod-hyhy", "prod-hyeu",
  * "prod-sphsph": geoopt constructors behind ManifoldFactory, sympa/embeddings.py:130-158, and VectorEmbeddings,

@@ -65,6 +65,7 @@ SYMBOLS = (
     "sympa_spd_egrad2rgrad",
     "sympa_spd_projx",
     "sympa_spd_rsgd_step",
+    "sympa_spd_radam_step",
     "sympa_vector_dist_fwd",
     "sympa_vector_model_forward",
     "sympa_vector_all_pairs_dist",
@@ -290,6 +291,10 @@ def load():
     lib.sympa_spd_rsgd_step.restype = ctypes.c_int
     lib.sympa_spd_rsgd_step.argtypes = [_c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
                                         ctypes.c_double, _c_double_p, ctypes.c_double, _c_i32_p, ctypes.c_void_p]
+    lib.sympa_spd_radam_step.restype = ctypes.c_int
+    lib.sympa_spd_radam_step.argtypes = [_c_double_p, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int,
+                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                         _c_double_p, _c_double_p, ctypes.c_double, _c_i32_p, ctypes.c_void_p]
     C = ctypes
     lib.sympa_vector_dist_fwd.restype = C.c_int
     lib.sympa_vector_dist_fwd.argtypes = [_c_double_p, _c_double_p, C.c_int64, C.c_int, C.c_int, _c_double_p, _c_i32_p, C.c_int,

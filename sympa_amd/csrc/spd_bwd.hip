@@ -1,5 +1,6 @@
 // gfx950 kernels + C-ABI of the SPD model's training path (spd_math_bwd.hpp): backward of the affine-invariant
-// distance with the fused AverageDistortionLoss, and the optimiser-side row operations (egrad2rgrad, projx, RSGD step).
+// distance with the fused AverageDistortionLoss, and the optimiser-side row operations (egrad2rgrad, projx, RSGD step, the
+// RiemannianAdam step: spd_radam_kernel here, sixteen lanes per row in spd_radam_coop*.hip).
 // Sixteen lanes per pair / per row for n >= 3 (spd_coop_bwd_kernel.hpp, spd_coop_table.hpp); the one-pair-per-lane kernels
 // below (runtime n <= 16, per-lane scratch) serve n <= 2, projx, and SYMPA_FLAG_GENERIC / SYMPA_SPD_TABLE_GENERIC=1 (A/B).
 // PARITY UNPINNED with respect to geoopt (absent); pinned by mpmath finite differences and autograd through the oracle.
@@ -111,15 +112,48 @@ __global__ __launch_bounds__(64) void spd_table_kernel(const int op, double* x, 
     }
 }
 
+// SYMPA_SPD_TABLE_GENERIC=1 keeps the one-row-per-lane kernels for A/B measurements (tools/spd_time.py); read once per process
+bool spd_table_generic() {
+    static const bool generic = std::getenv("SYMPA_SPD_TABLE_GENERIC") != nullptr;
+    return generic;
+}
+
+// RiemannianAdam step of the rows in place, one row per lane (spd_row_radam): n <= 2, SYMPA_SPD_TABLE_GENERIC=1, a demoted instantiation
+__global__ __launch_bounds__(64) void spd_radam_kernel(double* x, const double* g, double* m, double* s, const int64_t b, const int n,
+                                                       const double lr, const double beta1, const double beta2, const double eps_adam,
+                                                       const double wd, const double* pows, const double* clip, const double max_norm,
+                                                       int32_t* status) {
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    const bool live = i < b;
+    const int64_t ii = live ? i : b - 1;
+    const int nn = n * n;
+    sympa::SpdRowWork w;
+    int st = 0;
+    double row[sympa::SPD_MAX_N * sympa::SPD_MAX_N], mrow[sympa::SPD_MAX_N * sympa::SPD_MAX_N];
+    const double coef = (clip != nullptr) ? fmin(1.0, max_norm / (sqrt(clip[0]) + 1e-6)) : 1.0;
+    for (int k = 0; k < nn; ++k) { row[k] = x[ii * nn + k]; mrow[k] = m[ii * nn + k]; }
+    double sv = s[ii];
+    sympa::spd_row_radam(w, row, g + ii * nn, mrow, sv, n, lr, beta1, beta2, eps_adam, wd, coef, pows[0], pows[1], st);
+    if (live) {
+        for (int k = 0; k < nn; ++k) { x[i * nn + k] = row[k]; m[i * nn + k] = mrow[k]; }
+        s[i] = sv;
+    }
+    if (status != nullptr) {
+        const unsigned long long f = __ballot(live && st != 0);
+        if (f != 0ull) {
+            if (live && st != 0) atomicOr(&status[0], st);
+            if (threadIdx.x == 0) atomicAdd(&status[1], (int)__popcll(f));
+        }
+    }
+}
+
 int launch_spd_table(int op, double* x, const double* g, double* out, int64_t b, int n, double lr, double wd,
                      const double* clip, double max_norm, int32_t* projected, int32_t* status, void* stream) {
     if (b < 0) return fail(SYMPA_ERR_BAD_ARG, "negative row count");
     if (b == 0) return 0;
     if (x == nullptr) return fail(SYMPA_ERR_BAD_ARG, "null buffer");
     if (n < 1 || n > sympa::SPD_MAX_N) return fail(SYMPA_ERR_UNSUPPORTED_DIMS, "spd: dims outside [1, 16]");
-    // SYMPA_SPD_TABLE_GENERIC=1 keeps the one-row-per-lane kernel for A/B measurements (tools/spd_time.py)
-    static const bool generic = std::getenv("SYMPA_SPD_TABLE_GENERIC") != nullptr;
-    if (op != 0 && n >= SPD_COOP_BWD_MIN_N && !generic && !instance_fallback(SYMPA_FAMILY_SPD_TABLE, 0, n))
+    if (op != 0 && n >= SPD_COOP_BWD_MIN_N && !spd_table_generic() && !instance_fallback(SYMPA_FAMILY_SPD_TABLE, 0, n))
         launch_spd_coop_table(op, n, x, g, out, b, lr, wd, clip, max_norm, status, reinterpret_cast<hipStream_t>(stream));
     else
         hipLaunchKernelGGL(spd_table_kernel, dim3((unsigned)((b + 63) / 64)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
@@ -224,6 +258,29 @@ int sympa_spd_rsgd_step(double* table, const double* grad, int64_t num_rows, int
     if (num_rows > 0 && grad == nullptr) return fail(SYMPA_ERR_BAD_ARG, "null gradient");
     if (total_sqnorm != nullptr && !(max_norm > 0.0)) return fail(SYMPA_ERR_BAD_ARG, "max_norm must be > 0");
     return launch_spd_table(1, table, grad, nullptr, num_rows, n, lr, weight_decay, total_sqnorm, max_norm, nullptr, status, stream);
+}
+
+int sympa_spd_radam_step(double* table, const double* grad, double* exp_avg, double* exp_avg_sq, int64_t num_rows, int n,
+                         double lr, double beta1, double beta2, double eps_adam, double weight_decay, const double* bias_pows,
+                         const double* total_sqnorm, double max_norm, int32_t* status, void* stream) {
+    if (num_rows < 0) return fail(SYMPA_ERR_BAD_ARG, "negative row count");
+    if (num_rows == 0) return 0;
+    if (table == nullptr || grad == nullptr || exp_avg == nullptr || exp_avg_sq == nullptr || bias_pows == nullptr)
+        return fail(SYMPA_ERR_BAD_ARG, "null buffer");
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return fail(SYMPA_ERR_BAD_ARG, "betas must lie in [0, 1)");
+    if (!(eps_adam > 0.0)) return fail(SYMPA_ERR_BAD_ARG, "eps_adam must be > 0");
+    if (total_sqnorm != nullptr && !(max_norm > 0.0)) return fail(SYMPA_ERR_BAD_ARG, "max_norm must be > 0");
+    if (n < 1 || n > sympa::SPD_MAX_N) return fail(SYMPA_ERR_UNSUPPORTED_DIMS, "spd: dims outside [1, 16]");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (n >= SPD_COOP_BWD_MIN_N && !spd_table_generic() && !instance_fallback(SYMPA_FAMILY_SPD_TABLE, 0, n))
+        launch_spd_coop_radam(n, table, grad, exp_avg, exp_avg_sq, num_rows, lr, beta1, beta2, eps_adam, weight_decay, bias_pows,
+                              total_sqnorm, max_norm, status, s);
+    else
+        hipLaunchKernelGGL(spd_radam_kernel, dim3((unsigned)((num_rows + 63) / 64)), dim3(64), 0, s, table, grad, exp_avg, exp_avg_sq,
+                           num_rows, n, lr, beta1, beta2, eps_adam, weight_decay, bias_pows, total_sqnorm, max_norm, status);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail((int)e, hipGetErrorString(e));
+    return 0;
 }
 
 }  // extern "C"

@@ -47,6 +47,10 @@ inline dim3 spd_coop_bwd_grid(const int64_t b, const int n) {
 // egrad2rgrad (op 2) / RSGD step (op 1) with sixteen lanes per table row, n = 3..16 (spd_table_coop.hip)
 void launch_spd_coop_table(int op, int n, double* x, const double* g, double* out, int64_t b, double lr, double wd,
                            const double* clip, double max_norm, int32_t* status, hipStream_t s);
+// RiemannianAdam step with sixteen lanes per table row, n = 3..16 (spd_radam_coop.hip, spd_coop_radam.hpp)
+void launch_spd_coop_radam(int n, double* x, const double* g, double* m, double* sq, int64_t b, double lr, double beta1, double beta2,
+                           double eps_adam, double wd, const double* pows, const double* clip, double max_norm, int32_t* status,
+                           hipStream_t s);
 bool launch_spd_bwd_coop2_lo(const SpdBwdArgs& a, int n, hipStream_t s);             // two rounds per QL, n = 3..10
 bool launch_spd_bwd_coop2_hi(const SpdBwdArgs& a, int n, hipStream_t s);             // n = 11..16
 void launch_spd_coop_bwd_hi(const SpdBwdArgs& a, int n, dim3 grid, hipStream_t s);   // n = 12..15

@@ -394,4 +394,107 @@ SYMPA_HD void spd_row_rsgd(SpdRowWork& w, double* __restrict__ px, const double*
     if (!ok) status |= ST_NOT_PD;
 }
 
+// One RiemannianAdam step of a row in place: px = the point, pm = exp_avg ([n, n], read as sym(.)),
+// s = exp_avg_sq (ONE value per row), p1 / p2 = beta^t of this step.
+//   S = coef sym(g) + wd x,  r = sym(x S x),  I = || L^T S L ||_F^2 (x = L L^T),  m1 = b1 m + (1 - b1) r,  s1 = b2 s + (1 - b2) I,
+//   c = -lr / (1 - p1) / (sqrt(s1 / (1 - p2)) + eps),   y = retr(x, c m1) = x + c m1 + 1/2 c^2 A,   A = m1 x^-1 m1 = P P^T, P = m1 L^-T,
+//   m' = T(x -> y, m1) = m1 + c A + 1/2 c^2 B,   B = A x^-1 m1 = sym(R P^T), R = A L^-T
+// (the affine-invariant parallel transport along the step itself is this cubic in m1 x^-1: no eigendecomposition, no square root).
+// y and m' are stored symmetric bit for bit.  px and pm double as working storage: six n x n arrays in all.
+SYMPA_HD void spd_row_radam(SpdRowWork& w, double* __restrict__ px, const double* __restrict__ pg, double* __restrict__ pm,
+                            double& s, int n, double lr, double beta1, double beta2, double eps_adam, double wd, double coef,
+                            double p1, double p2, int& status) {
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            w.x[i * n + j] = 0.5 * (px[i * n + j] + px[j * n + i]);
+            w.u[i * n + j] = 0.5 * coef * (pg[i * n + j] + pg[j * n + i]);
+        }
+    if (wd != 0.0)
+        for (int k = 0; k < n * n; ++k) w.u[k] = d_fma(wd, w.x[k], w.u[k]);
+    // r = sym(x S x) into px
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            double t = 0.0;
+            for (int k = 0; k < n; ++k) t += w.x[i * n + k] * w.u[k * n + j];
+            w.t[i * n + j] = t;
+        }
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            double t = 0.0;
+            for (int k = 0; k < n; ++k) t += w.t[i * n + k] * w.x[k * n + j];
+            px[i * n + j] = t;
+        }
+    // m1 = b1 sym(m) + (1 - b1) sym(r) into pm
+    const double ob1 = 1.0 - beta1;
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j <= i; ++j) {
+            const double mm = 0.5 * (pm[i * n + j] + pm[j * n + i]);
+            const double rr = 0.5 * (px[i * n + j] + px[j * n + i]);
+            const double val = d_fma(beta1, mm, ob1 * rr);
+            pm[i * n + j] = val;
+            pm[j * n + i] = val;
+        }
+    const bool ok = spd_cholesky(w.x, n, w.l, w.rd);
+    // I = || L^T (S L) ||_F^2: a sum of squares, where tr((x S)(x S)) cancels by up to cond x
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            double t = 0.0;
+            for (int k = j; k < n; ++k) t += w.u[i * n + k] * w.l[k * n + j];
+            w.t[i * n + j] = t;
+        }
+    double inner = 0.0;
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            double t = 0.0;
+            for (int k = i; k < n; ++k) t += w.l[k * n + i] * w.t[k * n + j];
+            inner = d_fma(t, t, inner);
+        }
+    inner = fmax(inner, 0.0);
+    const double s1 = d_fma(beta2, s, (1.0 - beta2) * inner);
+    const double c = -lr / (1.0 - p1) / (d_sqrt(s1 / (1.0 - p2)) + eps_adam);
+    const double hc2 = 0.5 * c * c;
+    // P = m1 L^-T (rows) into w.t
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            double t = pm[i * n + j];
+            for (int k = 0; k < j; ++k) t -= w.t[i * n + k] * w.l[j * n + k];
+            w.t[i * n + j] = t * w.rd[j];
+        }
+    // A = P P^T into w.u, then y
+    for (int i = 0; i < n; ++i)
+        for (int j = i; j < n; ++j) {
+            double t = 0.0;
+            for (int k = 0; k < n; ++k) t += w.t[i * n + k] * w.t[j * n + k];
+            w.u[i * n + j] = t;
+            w.u[j * n + i] = t;
+        }
+    for (int i = 0; i < n; ++i)
+        for (int j = i; j < n; ++j) {
+            const double val = w.x[i * n + j] + c * pm[i * n + j] + hc2 * w.u[i * n + j];
+            px[i * n + j] = val;
+            px[j * n + i] = val;
+        }
+    // R = A L^-T into w.x, B = R P^T into w.l (the factor is spent once R stands)
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            double t = w.u[i * n + j];
+            for (int k = 0; k < j; ++k) t -= w.x[i * n + k] * w.l[j * n + k];
+            w.x[i * n + j] = t * w.rd[j];
+        }
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            double t = 0.0;
+            for (int k = 0; k < n; ++k) t += w.x[i * n + k] * w.t[j * n + k];
+            w.l[i * n + j] = t;
+        }
+    for (int i = 0; i < n; ++i)
+        for (int j = i; j < n; ++j) {
+            const double val = pm[i * n + j] + c * w.u[i * n + j] + hc2 * (0.5 * (w.l[i * n + j] + w.l[j * n + i]));
+            pm[i * n + j] = val;
+            pm[j * n + i] = val;
+        }
+    s = s1;
+    if (!ok) status |= ST_NOT_PD;
+}
+
 }  // namespace sympa

@@ -15,6 +15,21 @@ def _sym(x):
     return 0.5 * (x + x.transpose(-1, -2))
 
 
+def torch_radam_row(manifold, x, grad, exp_avg, exp_avg_sq, bias_pows, lr, betas=(0.9, 0.999), eps_adam=1e-8, weight_decay=0.0,
+                    coef=1.0):
+    """One RiemannianAdam step of an spd table in torch ops on any device, built on the manifold's own egrad2rgrad formula,
+    inner, retr and transp (what sympa_spd_radam_step computes in one kernel).  x, grad, exp_avg [N, n, n],
+    exp_avg_sq [N], bias_pows = (beta1^t, beta2^t) of this step.  Returns (y, exp_avg', exp_avg_sq'); the inputs are left alone."""
+    b1, b2 = betas
+    xs = _sym(x)
+    r = xs @ (coef * _sym(grad) + weight_decay * xs) @ xs
+    m1 = b1 * _sym(exp_avg) + (1.0 - b1) * r
+    s1 = b2 * exp_avg_sq + (1.0 - b2) * manifold.inner(xs, r).clamp_min(0.0)
+    c = -lr / (1.0 - bias_pows[0]) / ((s1 / (1.0 - bias_pows[1])).sqrt() + eps_adam)
+    y, mt = manifold.retr_transp(xs, c.reshape(-1, 1, 1) * m1, m1)
+    return y, _sym(mt), s1
+
+
 class SymmetricPositiveDefinite(Manifold):
     name = "SymmetricPositiveDefinite"
     ndim = 2
@@ -45,6 +60,28 @@ class SymmetricPositiveDefinite(Manifold):
         """geoopt: sym(x + u + 1/2 u x^-1 u), evaluated by the step kernel with lr = -1 on egrad-free input: host-side
         torch here (init / tests); the optimiser uses the fused sympa_spd_rsgd_step."""
         return _sym(x + u + 0.5 * u @ torch.linalg.inv(x) @ u)
+
+    def inner(self, x, u, v=None, keepdim=False):
+        """geoopt (AIM): tr(x^-1 u x^-1 v), one number per point; plain torch on any device."""
+        xu = torch.linalg.solve(x, u)
+        xv = xu if v is None else torch.linalg.solve(x, v)
+        out = (xu * xv.transpose(-1, -2)).sum((-1, -2))
+        return out.unsqueeze(-1).unsqueeze(-1) if keepdim else out
+
+    def component_inner(self, x, u, v=None):
+        """geoopt's default: the point's inner product, broadcast over the point's components."""
+        return self.inner(x, u, v, keepdim=True).expand_as(x)
+
+    def transp(self, x, y, v):
+        """Affine-invariant parallel transport of ANY tangent vector v along the geodesic x -> y, by its definition:
+        E v E^T with E = (y x^-1)^(1/2) = x^(1/2) (x^(-1/2) y x^(-1/2))^(1/2) x^(-1/2)  (two torch.linalg.eigh).  The step
+        kernel transports exp_avg along its own step, where this collapses to a cubic polynomial."""
+        lam, q = torch.linalg.eigh(_sym(x))
+        xh = q @ (lam.sqrt().unsqueeze(-1) * q.transpose(-1, -2))
+        xmh = q @ (lam.rsqrt().unsqueeze(-1) * q.transpose(-1, -2))
+        mu, w = torch.linalg.eigh(_sym(xmh @ _sym(y) @ xmh))
+        e = xh @ (w @ (mu.sqrt().unsqueeze(-1) * w.transpose(-1, -2))) @ xmh
+        return e @ v @ e.transpose(-1, -2)
 
     def _check_shape(self, shape, name):
         ok = len(shape) >= 2 and shape[-1] == shape[-2]

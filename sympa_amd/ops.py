@@ -1496,6 +1496,31 @@ def spd_rsgd_step_(table, grad, lr, weight_decay=0.0, clip_sqnorm=None, max_norm
     return table
 
 
+def spd_radam_step_(table, grad, exp_avg, exp_avg_sq, bias_pows, lr, betas=(0.9, 0.999), eps_adam=1e-8, weight_decay=0.0,
+                    clip_sqnorm=None, max_norm=None):
+    """In-place geoopt RiemannianAdam step over an spd table as ONE kernel (C-ABI sympa_spd_radam_step):
+    table / grad / exp_avg [N, n, n], exp_avg_sq [N] (one value per point), bias_pows = device tensor (beta1^t, beta2^t) of this
+    step.  exp_avg is parallel-transported to the new point along the step."""
+    lib = _lib.load()
+    _need_gpu(table, "table")
+    grad = _spd_rows(grad.detach(), "grad")
+    for name, t, shape in (("table", table, grad.shape), ("exp_avg", exp_avg, grad.shape), ("exp_avg_sq", exp_avg_sq, grad.shape[:1]),
+                           ("bias_pows", bias_pows, (2,))):
+        if t.dtype != torch.float64 or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != table.device:
+            raise ValueError(f"{name} must be a contiguous float64 tensor of shape {tuple(shape)} on {table.device}, got "
+                             f"{tuple(t.shape)} {t.dtype} on {t.device}")
+    _gate(_sc.SPD_TABLE, "spd", table.shape[1], table.device)
+    st = _status_buf(table.device)
+    with torch.cuda.device(table.device):
+        rc = lib.sympa_spd_radam_step(table.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), table.shape[0],
+                                      table.shape[1], float(lr), float(betas[0]), float(betas[1]), float(eps_adam),
+                                      float(weight_decay), bias_pows.data_ptr(),
+                                      None if clip_sqnorm is None else clip_sqnorm.data_ptr(),
+                                      float(max_norm) if max_norm is not None else 0.0, st.data_ptr(), _stream())
+    _lib.check(rc)
+    return table
+
+
 # ---------------------------------------------------------------------------------------------------
 # Vector models (C-ABI sympa_vector_*; DESIGN.md section 19): points are rows of `dims` doubles
 # ---------------------------------------------------------------------------------------------------

@@ -105,7 +105,9 @@ class RiemannianAdam(torch.optim.Optimizer):
     (= projx(x + u)) are HIP kernels over the table rows; the moment updates are elementwise torch ops on the device.
     A table of a vector model (euclidean, poincare, lorentz, sphere, the products) on the device takes the same step per factor
     as ONE kernel over its rows (sympa_vector_radam_step): exp_avg_sq has the table's shape, and exp_avg is
-    parallel-transported to the new point.  Parameters without a manifold get the ordinary Adam update.  amsgrad is not built.
+    parallel-transported to the new point.  An spd table on the device likewise takes ONE kernel (sympa_spd_radam_step, DESIGN.md
+    section 21): exp_avg_sq is [N], one value per point, and exp_avg is carried to the new point by the affine-invariant parallel
+    transport along the step.  Parameters without a manifold get the ordinary Adam update.  amsgrad is not built.
 
     The powers b1^t, b2^t live in two device words per parameter and are advanced by the step itself, so nothing the step
     computes depends on host state that changes from call to call: the step can be captured in a hipGraph
@@ -133,7 +135,8 @@ class RiemannianAdam(torch.optim.Optimizer):
         moments AND in the bias corrections from the next step on (the powers restart from the new betas at the same t)."""
         state = self.state[p]
         manifold = getattr(p, "manifold", None)
-        siegel = isinstance(manifold, SiegelManifold) and p.is_cuda
+        # one second moment per point: a Siegel table on the device, an spd table anywhere
+        siegel = (isinstance(manifold, SiegelManifold) and p.is_cuda) or isinstance(manifold, SymmetricPositiveDefinite)
         if "exp_avg" not in state:
             state["exp_avg"] = torch.zeros_like(p)
         if "exp_avg_sq" not in state:
@@ -192,8 +195,10 @@ class RiemannianAdam(torch.optim.Optimizer):
                 siegel = isinstance(manifold, SiegelManifold) and p.is_cuda
                 if manifold is not None:
                     ops.table_changed(p)       # (see RiemannianSGD.step)
-                if isinstance(manifold, SymmetricPositiveDefinite):
-                    raise NotImplementedError("RiemannianAdam on the spd model needs geoopt's parallel transport: use rsgd")
+                if isinstance(manifold, SymmetricPositiveDefinite) and not p.is_cuda:
+                    raise NotImplementedError("RiemannianAdam on the spd table is one HIP kernel over the table "
+                                              "(sympa_spd_radam_step) and is not built for a table on the host: move the model to "
+                                              "the device, or use rsgd")
                 if isinstance(manifold, VectorManifold) and not p.is_cuda:
                     raise NotImplementedError("RiemannianAdam on a vector model's table is one HIP kernel over the table "
                                               "(sympa_vector_radam_step) and is not built for a table on the host: move the model "
@@ -207,6 +212,12 @@ class RiemannianAdam(torch.optim.Optimizer):
                     # the whole row update in one kernel: moments, retraction, the parallel transport of exp_avg to the new point
                     ops.vector_radam_step_(p.data, p.grad, m, v, state["bias_pows"], manifold.model_name, lr, (b1, b2), eps, wd,
                                            counter=manifold.projected_counter(p.device))
+                    continue
+                if isinstance(manifold, SymmetricPositiveDefinite):
+                    if p.dtype != torch.float64:
+                        raise TypeError("the spd table must be float64 (config.py:17-18)")
+                    # the whole row update in one kernel: moments, geoopt's retraction, exp_avg transported along the step
+                    ops.spd_radam_step_(p.data, p.grad, m, v, state["bias_pows"], lr, (b1, b2), eps, wd)
                     continue
                 if siegel and p.shape[2] <= ops.RADAM_FUSED_MAX_DIMS and p.data.is_contiguous() and p.dtype == torch.float64:
                     # the whole row update in one kernel (C-ABI sympa_radam_step); the powers were advanced just above

@@ -178,10 +178,18 @@ def _check_spd_table(model, n, dev):
     grad = torch.randn(table.shape, generator=g, dtype=torch.float64)
     grad = (0.5 * (grad + grad.transpose(-1, -2))).to(dev)
 
+    # one RiemannianAdam step from a non-zero state (sympa_spd_radam_step): a tangent exp_avg, exp_avg_sq > 0, the powers of t = 3
+    m0 = table @ (0.3 * grad.flip(0)) @ table
+    m0 = 0.5 * (m0 + m0.transpose(-1, -2))
+    s0 = torch.linspace(0.5, 2.0, table.shape[0], dtype=torch.float64, device=dev)
+    pows = torch.tensor([0.9 ** 3, 0.999 ** 3], dtype=torch.float64, device=dev)
+
     def run():
         t = table.clone()
         ops.spd_rsgd_step_(t, grad, 1e-2)
-        return [ops.spd_egrad2rgrad(table, grad), t]
+        ta, ma, sa = table.clone(), m0.clone(), s0.clone()
+        ops.spd_radam_step_(ta, grad, ma, sa, pows, 1e-2, (0.9, 0.999), 1e-7, 0.0)
+        return [ops.spd_egrad2rgrad(table, grad), t, ta, ma, sa]
 
     fast = run()
     with _OneLane(SPD_TABLE, "spd", n):

@@ -8,6 +8,7 @@ rewrite of them: SURVEY 8f): graph -> triplets -> Model -> fused training step -
     python tools/train_siegel.py --graph grid3d-125 --subsample 0.25 --scale_triplets
     python tools/train_siegel.py --graph product-cartesian-45500 --dims 8 --sampled-pairs 1048576 --batch_size 262144 --subsample 0.01
     python tools/train_siegel.py --graph grid3d-125 --manifold poincare --optim radam --dims 4
+    python tools/train_siegel.py --graph grid3d-125 --manifold spd --optim radam --dims 3
 
 Per batch it runs exactly two kernels: sympa_model_loss_backward (forward + AverageDistortionLoss + backward +
 scatter, runner.py:101-105) and sympa_rsgd_step (geoopt RiemannianSGD, train.py:66-68), plus the gradient clip
