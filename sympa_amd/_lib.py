@@ -1,95 +1,22 @@
 """ctypes binding of the C-ABI in include/sympa_hip.h.
 
+The header is READ, not mirrored: parse_header() takes every prototype and every integer #define from its text at import
+(PROTOTYPES, SYMBOLS, DEFINES), and bind() sets the types of every declared entry on a library handle.  A
+declaration the type table below cannot express is an error that names it, never a guess.
+
 The product path has NO fallback: if libsympa_hip.so is missing or does not export a declared
 symbol, importing/using the ops raises.  (Build it with `python -c "import __graft_entry__ as g; g.build()"`;
 `make -C sympa_amd/csrc` runs the same function -- there is ONE build path, the one that scans every translation
 unit's ISA for the DPP hazard and rebuilds the units that show it.)"""
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SYMPA_HIP_LIB: another BUILD of the same library (tools/build_variant.sh: A/B timing, compiler-flag experiments); never a
-# different implementation -- the symbol check below applies to it as well
+# different implementation -- the symbol check of bind() applies to it as well
 LIB_PATH = os.environ.get("SYMPA_HIP_LIB") or os.path.join(_HERE, "csrc", "libsympa_hip.so")
-
-# every symbol include/sympa_hip.h declares (tests check the header against this list)
-SYMBOLS = (
-    "sympa_version",
-    "sympa_last_error",
-    "sympa_max_dims",
-    "sympa_set_instance_fallback",
-    "sympa_get_instance_fallback",
-    "sympa_siegel_dist_fwd",
-    "sympa_model_forward",
-    "sympa_model_forward_batches",
-    "sympa_table_pack_bytes",
-    "sympa_table_pack",
-    "sympa_table_digest",
-    "sympa_clock_stamp",
-    "sympa_table_pack_refresh",
-    "sympa_model_forward_packed",
-    "sympa_model_forward_batches_packed",
-    "sympa_all_pairs_dist",
-    "sympa_all_pairs_workspace_bytes",
-    "sympa_all_pairs_dist_packed",
-    "sympa_siegel_backward_workspace_bytes",
-    "sympa_siegel_dist_bwd",
-    "sympa_model_backward",
-    "sympa_model_loss_backward",
-    "sympa_model_loss_backward_rows",
-    "sympa_scatter_add_rows",
-    "sympa_egrad2rgrad",
-    "sympa_tangent_sqnorm",
-    "sympa_projx",
-    "sympa_rsgd_step",
-    "sympa_radam_step",
-    "sympa_radam_step_fused",
-    "sympa_sqnorm_accum",
-    "sympa_sgd_step_clipped",
-    "sympa_rsgd_step_clipped",
-    "sympa_model_train_backward",
-    "sympa_segment_sum_rows",
-    "sympa_segment_sum_partials",
-    "sympa_rsgd_step_fused_workspace_bytes",
-    "sympa_rsgd_step_fused",
-    "sympa_spd_dist_fwd",
-    "sympa_spd_model_forward",
-    "sympa_spd_table_pack_bytes",
-    "sympa_spd_table_pack",
-    "sympa_spd_table_pack_refresh",
-    "sympa_spd_model_forward_packed",
-    "sympa_scatter_add_flat_rows",
-    "sympa_spd_backward_rows",
-    "sympa_spd_backward_workspace_bytes",
-    "sympa_spd_loss_backward",
-    "sympa_spd_egrad2rgrad",
-    "sympa_spd_projx",
-    "sympa_spd_rsgd_step",
-    "sympa_spd_radam_step",
-    "sympa_vector_dist_fwd",
-    "sympa_vector_model_forward",
-    "sympa_vector_all_pairs_dist",
-    "sympa_vector_backward_rows",
-    "sympa_vector_egrad2rgrad",
-    "sympa_vector_projx",
-    "sympa_vector_rsgd_step",
-    "sympa_vector_radam_step",
-    "sympa_map_workspace_bytes",
-    "sympa_map_rows",
-    "sympa_graph_hops_workspace_bytes",
-    "sympa_graph_hop_rows",
-    "sympa_graph_distortion_rows",
-    "sympa_graph_weighted_workspace_bytes",
-    "sympa_graph_weighted_rows",
-    "sympa_graph_weighted_distortion_rows",
-    "sympa_graph_hop_census_rows",
-    "sympa_graph_ball_count_rows",
-    "sympa_graph_ball_select_rows",
-)
-
-_c_double_p = ctypes.c_void_p
-_c_i64_p = ctypes.c_void_p
-_c_i32_p = ctypes.c_void_p
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sympa_hip.h")
 
 _lib = None
 _fast = None          # sympa_amd/_fast.<abi>.so (csrc/torch_binding.cpp) once bound; False when absent or switched off
@@ -97,6 +24,62 @@ _fast = None          # sympa_amd/_fast.<abi>.so (csrc/torch_binding.cpp) once b
 
 class SympaHipError(RuntimeError):
     pass
+
+
+# the C types of the header: by value these three, every pointer as an address, `const char*` only as a return
+_BY_VALUE = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double}
+_DECLARATION = re.compile(r"([\w\s*]+?)\b(sympa_\w+)\s*\(([^();]*)\)\s*;")
+_DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(SYMPA_\w+)(.*)$", re.M)
+
+
+def parse_header(text):
+    """The prototypes of the header `text` in file order, name -> (return type, [parameter types]), and its integer
+    defines, name -> int."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)       # the comments quote calls like sympa_model_forward(...)
+    defines = {}
+    for name, value in _DEFINE.findall(text):
+        m = re.fullmatch(r"\s*(?:(\d+)|\((-?\d+)\))\s*", value)
+        if m:
+            defines[name] = int(m.group(1) or m.group(2))
+        elif value.strip():                                  # no value at all: the include guard
+            raise SympaHipError(f"sympa_hip.h: #define {name} is not an integer: {value.strip()!r}")
+    code = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    prototypes = {}
+    for m in _DECLARATION.finditer(code):
+        ret, name, params = " ".join(m.group(1).split()), m.group(2), m.group(3).strip()
+        if name in prototypes:
+            raise SympaHipError(f"sympa_hip.h: {name} is declared twice")
+        if ret == "const char*":
+            restype = ctypes.c_char_p
+        elif ret in _BY_VALUE:
+            restype = _BY_VALUE[ret]
+        else:
+            raise SympaHipError(f"sympa_hip.h: {name}: no ctypes type for the return type {ret!r}")
+        types = []
+        for p in [] if params == "void" else params.split(","):
+            by_value = re.fullmatch(r"\s*(\w+)\s+\w+\s*", p)     # `type name`
+            if "*" in p:
+                types.append(ctypes.c_void_p)
+            elif by_value and by_value.group(1) in _BY_VALUE:
+                types.append(_BY_VALUE[by_value.group(1)])
+            else:
+                raise SympaHipError(f"sympa_hip.h: {name}: no ctypes type for the parameter {p.strip()!r}")
+        prototypes[name] = (restype, types)
+    left = re.search(r"sympa_\w*\s*\(", _DECLARATION.sub(";", code))
+    if left:
+        raise SympaHipError(f"sympa_hip.h: cannot read the declaration at {left.group(0)!r}")
+    return prototypes, defines
+
+
+def read_header():
+    if not os.path.exists(HEADER_PATH):
+        raise SympaHipError(f"{HEADER_PATH} not found: the ctypes prototypes and the SYMPA_* constants are read from it")
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read())
+
+
+PROTOTYPES, DEFINES = read_header()
+SYMBOLS = tuple(PROTOTYPES)     # every symbol include/sympa_hip.h declares (the tests read the header with a regex of their own)
 
 
 def fast():
@@ -119,6 +102,17 @@ def fast():
     return _fast or None
 
 
+def bind(cdll):
+    """Sets the header's prototypes on a handle of (a build of) the library, which must export every declared symbol."""
+    for s in SYMBOLS:
+        if not hasattr(cdll, s):
+            raise SympaHipError(f"{getattr(cdll, '_name', cdll)} does not export {s}")
+    for s, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(cdll, s)
+        fn.restype, fn.argtypes = restype, argtypes
+    return cdll
+
+
 def load():
     """Loads libsympa_hip.so once and sets the prototypes.  Raises SympaHipError when absent."""
     global _lib
@@ -129,260 +123,8 @@ def load():
             f"{LIB_PATH} not found: the HIP extension is not built. There is no CPU fallback; "
             "run __graft_entry__.build() (hipcc --offload-arch=gfx950)."
         )
-    lib = ctypes.CDLL(LIB_PATH)
-    for s in SYMBOLS:
-        if not hasattr(lib, s):
-            raise SympaHipError(f"{LIB_PATH} does not export {s}")
-    lib.sympa_version.restype = ctypes.c_char_p
-    lib.sympa_last_error.restype = ctypes.c_char_p
-    lib.sympa_max_dims.restype = ctypes.c_int
-    lib.sympa_set_instance_fallback.restype = ctypes.c_int
-    lib.sympa_set_instance_fallback.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    lib.sympa_get_instance_fallback.restype = ctypes.c_int
-    lib.sympa_get_instance_fallback.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    lib.sympa_siegel_dist_fwd.restype = ctypes.c_int
-    lib.sympa_siegel_dist_fwd.argtypes = [
-        _c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-        _c_double_p, ctypes.c_double, _c_double_p, _c_double_p, _c_i32_p, ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.sympa_model_forward.restype = ctypes.c_int
-    lib.sympa_model_forward.argtypes = [
-        _c_double_p, ctypes.c_int64, ctypes.c_int, _c_i64_p, ctypes.c_int64, _c_i64_p, ctypes.c_int64,
-        ctypes.c_int64, ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_double, _c_double_p,
-        ctypes.c_double, _c_double_p, _c_i32_p, ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.sympa_model_forward_batches.restype = ctypes.c_int
-    lib.sympa_model_forward_batches.argtypes = [
-        _c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
-        ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_double, _c_double_p, ctypes.c_double, ctypes.c_void_p,
-        _c_i32_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
-    ]
-    lib.sympa_all_pairs_dist.restype = ctypes.c_int
-    lib.sympa_all_pairs_dist.argtypes = [
-        _c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-        _c_double_p, ctypes.c_double, _c_double_p, ctypes.c_double, _c_double_p, _c_i32_p, ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.sympa_all_pairs_workspace_bytes.restype = ctypes.c_int64
-    lib.sympa_all_pairs_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int]
-    lib.sympa_all_pairs_dist_packed.restype = ctypes.c_int
-    lib.sympa_all_pairs_dist_packed.argtypes = [
-        _c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-        _c_double_p, ctypes.c_double, _c_double_p, ctypes.c_double, _c_double_p, ctypes.c_void_p, ctypes.c_int64,
-        _c_i32_p, ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.sympa_siegel_dist_bwd.restype = ctypes.c_int
-    lib.sympa_siegel_dist_bwd.argtypes = [
-        _c_double_p, _c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-        _c_double_p, ctypes.c_double, _c_double_p, _c_double_p, _c_double_p, _c_i32_p, ctypes.c_void_p, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.sympa_siegel_backward_workspace_bytes.restype = ctypes.c_int64
-    lib.sympa_siegel_backward_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int]
-    lib.sympa_model_backward.restype = ctypes.c_int
-    lib.sympa_model_backward.argtypes = [
-        _c_double_p, ctypes.c_int64, ctypes.c_int, _c_i64_p, ctypes.c_int64, _c_i64_p, ctypes.c_int64,
-        ctypes.c_int64, ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_double, _c_double_p, ctypes.c_double,
-        _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_i32_p, ctypes.c_void_p, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.sympa_model_loss_backward.restype = ctypes.c_int
-    lib.sympa_model_loss_backward.argtypes = [
-        _c_double_p, ctypes.c_int64, ctypes.c_int, _c_i64_p, ctypes.c_int64, _c_i64_p, ctypes.c_int64, _c_double_p,
-        ctypes.c_int64, ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_double, _c_double_p, ctypes.c_double,
-        ctypes.c_double, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_i32_p, ctypes.c_void_p,
-        ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.sympa_model_loss_backward_rows.restype = ctypes.c_int
-    lib.sympa_model_loss_backward_rows.argtypes = [
-        _c_double_p, ctypes.c_int64, ctypes.c_int, _c_i64_p, ctypes.c_int64, _c_i64_p, ctypes.c_int64, _c_double_p,
-        ctypes.c_int64, ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_double, _c_double_p, ctypes.c_double,
-        ctypes.c_double, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_i32_p,
-        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.sympa_scatter_add_rows.restype = ctypes.c_int
-    lib.sympa_scatter_add_rows.argtypes = [_c_double_p, _c_i64_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
-                                           ctypes.c_int64, ctypes.c_double, _c_double_p, _c_i32_p, ctypes.c_void_p]
-    lib.sympa_egrad2rgrad.restype = ctypes.c_int
-    lib.sympa_egrad2rgrad.argtypes = [_c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _c_double_p,
-                                      ctypes.c_void_p]
-    lib.sympa_tangent_sqnorm.restype = ctypes.c_int
-    lib.sympa_tangent_sqnorm.argtypes = [_c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _c_double_p,
-                                         _c_i32_p, ctypes.c_void_p]
-    lib.sympa_projx.restype = ctypes.c_int
-    lib.sympa_projx.argtypes = [_c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_double_p,
-                                _c_i32_p, _c_i32_p, _c_i32_p, ctypes.c_void_p]
-    lib.sympa_model_train_backward.restype = ctypes.c_int
-    lib.sympa_model_train_backward.argtypes = [
-        _c_double_p, ctypes.c_int64, ctypes.c_int, _c_i64_p, ctypes.c_int64, _c_i64_p, ctypes.c_int64, _c_double_p,
-        ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_double, _c_double_p,
-        ctypes.c_double, ctypes.c_double, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
-        _c_i32_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.sympa_segment_sum_rows.restype = ctypes.c_int
-    lib.sympa_segment_sum_rows.argtypes = [
-        _c_double_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p,
-        ctypes.c_double, ctypes.c_int, _c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _c_double_p,
-        _c_double_p, _c_double_p, _c_double_p, ctypes.c_void_p,
-    ]
-    lib.sympa_segment_sum_partials.restype = ctypes.c_int64
-    lib.sympa_segment_sum_partials.argtypes = [ctypes.c_int64, ctypes.c_int]
-    lib.sympa_rsgd_step_fused_workspace_bytes.restype = ctypes.c_int64
-    lib.sympa_rsgd_step_fused_workspace_bytes.argtypes = [ctypes.c_int64]
-    lib.sympa_radam_step_fused.restype = ctypes.c_int
-    lib.sympa_radam_step_fused.argtypes = [
-        _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-        ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-        ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, _c_double_p, ctypes.c_int,
-        ctypes.c_void_p, _c_i32_p, _c_i32_p, ctypes.c_void_p,
-    ]
-    lib.sympa_rsgd_step_fused.restype = ctypes.c_int
-    lib.sympa_rsgd_step_fused.argtypes = [
-        _c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
-        ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, _c_double_p, ctypes.c_int, ctypes.c_void_p, _c_i32_p,
-        _c_i32_p, ctypes.c_void_p,
-    ]
-    lib.sympa_radam_step.restype = ctypes.c_int
-    lib.sympa_radam_step.argtypes = [_c_double_p, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                                     ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                     _c_double_p, ctypes.c_double, _c_i32_p, _c_i32_p, ctypes.c_void_p]
-    lib.sympa_rsgd_step.restype = ctypes.c_int
-    lib.sympa_rsgd_step.argtypes = [_c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double,
-                                    ctypes.c_double, ctypes.c_double, _c_i32_p, _c_i32_p, _c_i32_p, ctypes.c_void_p]
-    lib.sympa_sqnorm_accum.restype = ctypes.c_int
-    lib.sympa_sqnorm_accum.argtypes = [_c_double_p, ctypes.c_int64, _c_double_p, ctypes.c_void_p]
-    lib.sympa_sgd_step_clipped.restype = ctypes.c_int
-    lib.sympa_sgd_step_clipped.argtypes = [_c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
-                                           _c_double_p, ctypes.c_double, ctypes.c_void_p]
-    lib.sympa_rsgd_step_clipped.restype = ctypes.c_int
-    lib.sympa_rsgd_step_clipped.argtypes = [_c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                                            ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_double_p,
-                                            ctypes.c_double, _c_i32_p, _c_i32_p, _c_i32_p, ctypes.c_void_p]
-    lib.sympa_spd_dist_fwd.restype = ctypes.c_int
-    lib.sympa_spd_dist_fwd.argtypes = [_c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int, _c_double_p, _c_i32_p,
-                                       ctypes.c_int, ctypes.c_void_p]
-    lib.sympa_spd_model_forward.restype = ctypes.c_int
-    lib.sympa_spd_model_forward.argtypes = [_c_double_p, ctypes.c_int64, ctypes.c_int, _c_i64_p, ctypes.c_int64, _c_i64_p,
-                                            ctypes.c_int64, ctypes.c_int64, _c_double_p, ctypes.c_double, _c_double_p,
-                                            _c_i32_p, ctypes.c_int, ctypes.c_void_p]
-    lib.sympa_scatter_add_flat_rows.restype = ctypes.c_int
-    lib.sympa_scatter_add_flat_rows.argtypes = [_c_double_p, _c_i64_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
-                                                ctypes.c_int64, ctypes.c_double, _c_double_p, _c_i32_p, ctypes.c_void_p]
-    lib.sympa_spd_backward_rows.restype = ctypes.c_int
-    lib.sympa_spd_backward_rows.argtypes = [
-        _c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int, _c_i64_p, ctypes.c_int64, _c_i64_p, ctypes.c_int64,
-        ctypes.c_int64, _c_double_p, ctypes.c_double, _c_double_p, _c_double_p, ctypes.c_double, _c_double_p,
-        _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_i32_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
-        ctypes.c_void_p,
-    ]
-    lib.sympa_spd_backward_workspace_bytes.restype = ctypes.c_int64
-    lib.sympa_spd_backward_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int]
-    lib.sympa_spd_loss_backward.restype = ctypes.c_int
-    lib.sympa_spd_loss_backward.argtypes = [
-        _c_double_p, ctypes.c_int64, ctypes.c_int, _c_i64_p, ctypes.c_int64, _c_i64_p, ctypes.c_int64, ctypes.c_int64,
-        _c_double_p, ctypes.c_double, _c_double_p, _c_double_p, ctypes.c_double, _c_double_p, _c_double_p, _c_double_p,
-        _c_double_p, _c_i32_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.sympa_spd_egrad2rgrad.restype = ctypes.c_int
-    lib.sympa_spd_egrad2rgrad.argtypes = [_c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int, _c_double_p, ctypes.c_void_p]
-    lib.sympa_spd_projx.restype = ctypes.c_int
-    lib.sympa_spd_projx.argtypes = [_c_double_p, ctypes.c_int64, ctypes.c_int, _c_double_p, _c_i32_p, _c_i32_p, ctypes.c_void_p]
-    lib.sympa_spd_rsgd_step.restype = ctypes.c_int
-    lib.sympa_spd_rsgd_step.argtypes = [_c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
-                                        ctypes.c_double, _c_double_p, ctypes.c_double, _c_i32_p, ctypes.c_void_p]
-    lib.sympa_spd_radam_step.restype = ctypes.c_int
-    lib.sympa_spd_radam_step.argtypes = [_c_double_p, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int,
-                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                         _c_double_p, _c_double_p, ctypes.c_double, _c_i32_p, ctypes.c_void_p]
-    C = ctypes
-    lib.sympa_vector_dist_fwd.restype = C.c_int
-    lib.sympa_vector_dist_fwd.argtypes = [_c_double_p, _c_double_p, C.c_int64, C.c_int, C.c_int, _c_double_p, _c_i32_p, C.c_int,
-                                          C.c_void_p]
-    lib.sympa_vector_model_forward.restype = C.c_int
-    lib.sympa_vector_model_forward.argtypes = [_c_double_p, C.c_int64, C.c_int, _c_i64_p, C.c_int64, _c_i64_p, C.c_int64, C.c_int64,
-                                               C.c_int, _c_double_p, C.c_double, _c_double_p, _c_i32_p, C.c_int, C.c_void_p]
-    lib.sympa_vector_all_pairs_dist.restype = C.c_int
-    lib.sympa_vector_all_pairs_dist.argtypes = [_c_double_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, _c_double_p,
-                                                C.c_double, _c_double_p, _c_i32_p, C.c_int, C.c_void_p]
-    lib.sympa_vector_backward_rows.restype = C.c_int
-    lib.sympa_vector_backward_rows.argtypes = [
-        _c_double_p, _c_double_p, C.c_int64, C.c_int, C.c_int, _c_i64_p, C.c_int64, _c_i64_p, C.c_int64, C.c_int64, _c_double_p,
-        C.c_double, _c_double_p, _c_double_p, C.c_double, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
-        _c_i32_p, C.c_int, C.c_void_p]
-    lib.sympa_vector_egrad2rgrad.restype = C.c_int
-    lib.sympa_vector_egrad2rgrad.argtypes = [_c_double_p, _c_double_p, C.c_int64, C.c_int, C.c_int, _c_double_p, C.c_void_p]
-    lib.sympa_vector_projx.restype = C.c_int
-    lib.sympa_vector_projx.argtypes = [_c_double_p, C.c_int64, C.c_int, C.c_int, _c_double_p, _c_i32_p, _c_i32_p, C.c_void_p]
-    lib.sympa_vector_rsgd_step.restype = C.c_int
-    lib.sympa_vector_rsgd_step.argtypes = [_c_double_p, _c_double_p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double,
-                                           _c_double_p, C.c_double, _c_i32_p, _c_i32_p, C.c_void_p]
-    lib.sympa_vector_radam_step.restype = C.c_int
-    lib.sympa_vector_radam_step.argtypes = [_c_double_p, _c_double_p, _c_double_p, _c_double_p, C.c_int64, C.c_int, C.c_int,
-                                            C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _c_double_p, _c_double_p,
-                                            C.c_double, _c_i32_p, _c_i32_p, C.c_void_p]
-    lib.sympa_table_pack_bytes.restype = C.c_int64
-    lib.sympa_table_pack_bytes.argtypes = [C.c_int64, C.c_int, C.c_int]
-    lib.sympa_table_pack.restype = C.c_int
-    lib.sympa_table_pack.argtypes = [_c_double_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, _c_i32_p, C.c_void_p]
-    lib.sympa_clock_stamp.restype = C.c_int
-    lib.sympa_clock_stamp.argtypes = [C.c_void_p, C.c_void_p]
-    lib.sympa_table_digest.restype = C.c_int
-    lib.sympa_table_digest.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
-    lib.sympa_table_pack_refresh.restype = C.c_int
-    lib.sympa_table_pack_refresh.argtypes = [_c_double_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
-                                             _c_i32_p, C.c_void_p]
-    lib.sympa_spd_table_pack_refresh.restype = C.c_int
-    lib.sympa_spd_table_pack_refresh.argtypes = [_c_double_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, _c_i32_p,
-                                                 C.c_void_p]
-    lib.sympa_model_forward_packed.restype = C.c_int
-    lib.sympa_model_forward_packed.argtypes = [
-        C.c_void_p, C.c_int64, C.c_int64, C.c_int, _c_i64_p, C.c_int64, _c_i64_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
-        _c_double_p, C.c_double, _c_double_p, C.c_double, _c_double_p, _c_i32_p, C.c_int, C.c_void_p]
-    lib.sympa_model_forward_batches_packed.restype = C.c_int
-    lib.sympa_model_forward_batches_packed.argtypes = [
-        C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
-        _c_double_p, C.c_double, _c_double_p, C.c_double, C.c_void_p, _c_i32_p, C.c_int, C.c_void_p]
-    lib.sympa_spd_table_pack_bytes.restype = C.c_int64
-    lib.sympa_spd_table_pack_bytes.argtypes = [C.c_int64, C.c_int]
-    lib.sympa_spd_table_pack.restype = C.c_int
-    lib.sympa_spd_table_pack.argtypes = [_c_double_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, _c_i32_p, C.c_void_p]
-    lib.sympa_spd_model_forward_packed.restype = C.c_int
-    lib.sympa_spd_model_forward_packed.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, _c_i64_p, C.c_int64, _c_i64_p,
-                                                   C.c_int64, C.c_int64, _c_double_p, C.c_double, _c_double_p, _c_i32_p, C.c_int,
-                                                   C.c_void_p]
-    lib.sympa_map_workspace_bytes.restype = C.c_int64
-    lib.sympa_map_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
-    lib.sympa_map_rows.restype = C.c_int
-    lib.sympa_map_rows.argtypes = [_c_double_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _c_i64_p, _c_i32_p, C.c_int64,
-                                   _c_double_p, C.c_void_p, C.c_int64, _c_i32_p, C.c_int, C.c_void_p]
-    lib.sympa_graph_hops_workspace_bytes.restype = C.c_int64
-    lib.sympa_graph_hops_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
-    lib.sympa_graph_hop_rows.restype = C.c_int
-    lib.sympa_graph_hop_rows.argtypes = [_c_i64_p, _c_i32_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _c_i32_p, C.c_int64,
-                                         C.c_void_p, C.c_int64, _c_i32_p, C.c_void_p]
-    lib.sympa_graph_distortion_rows.restype = C.c_int
-    lib.sympa_graph_distortion_rows.argtypes = [_c_double_p, C.c_int64, _c_i32_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
-                                                _c_double_p, _c_i64_p, C.c_void_p]
-    lib.sympa_graph_weighted_workspace_bytes.restype = C.c_int64
-    lib.sympa_graph_weighted_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
-    lib.sympa_graph_weighted_rows.restype = C.c_int
-    lib.sympa_graph_weighted_rows.argtypes = [_c_i64_p, _c_i32_p, _c_double_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
-                                              _c_double_p, C.c_int64, C.c_void_p, C.c_int64, _c_i32_p, C.c_void_p]
-    lib.sympa_graph_weighted_distortion_rows.restype = C.c_int
-    lib.sympa_graph_weighted_distortion_rows.argtypes = [_c_double_p, C.c_int64, _c_double_p, C.c_int64, C.c_int64, C.c_int64,
-                                                         C.c_int64, _c_double_p, _c_i64_p, C.c_void_p]
-    lib.sympa_graph_hop_census_rows.restype = C.c_int
-    lib.sympa_graph_hop_census_rows.argtypes = [_c_i32_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _c_i64_p, C.c_int64,
-                                                C.c_void_p]
-    lib.sympa_graph_ball_count_rows.restype = C.c_int
-    lib.sympa_graph_ball_count_rows.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double,
-                                                _c_i64_p, C.c_void_p]
-    lib.sympa_graph_ball_select_rows.restype = C.c_int
-    lib.sympa_graph_ball_select_rows.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double,
-                                                 _c_i64_p, _c_i64_p, C.c_int64, _c_i64_p, _c_double_p, _c_i32_p, C.c_void_p]
-    _lib = lib
-    return lib
+    _lib = bind(ctypes.CDLL(LIB_PATH))
+    return _lib
 
 
 def check(rc):

@@ -15,12 +15,15 @@ from sympa_amd import _lib
 from sympa_amd import selfcheck as _sc
 from sympa_amd.config import EPS
 
-MODEL_IDS = {"upper": 0, "bounded": 1, "dual": 2}
+# every id, status bit and flag below is read from include/sympa_hip.h (_lib.DEFINES), the one place that states them
+_D = _lib.DEFINES
+MODEL_IDS = {"upper": _D["SYMPA_MODEL_UPPER"], "bounded": _D["SYMPA_MODEL_BOUNDED"], "dual": _D["SYMPA_MODEL_DUAL"]}
 # the compact dual runs the one-pair-per-lane and runtime-n kernels only: no packed table, no lanes-per-pair instances, no fused step
 LANES_PER_PAIR_MODELS = ("upper", "bounded")
-METRIC_IDS = {"riem": 0, "fone": 1, "finf": 2, "fmin": 3, "wsum": 4}
+METRIC_IDS = {m: _D["SYMPA_METRIC_" + m.upper()] for m in ("riem", "fone", "finf", "fmin", "wsum")}
 
-ST_NOT_PD, ST_NONFINITE, ST_BAD_INDEX, ST_NO_CONVERGENCE = 1, 2, 4, 8
+ST_NOT_PD, ST_NONFINITE, ST_BAD_INDEX, ST_NO_CONVERGENCE = (
+    _D["SYMPA_ST_NOT_PD"], _D["SYMPA_ST_NONFINITE"], _D["SYMPA_ST_BAD_INDEX"], _D["SYMPA_ST_NO_CONVERGENCE"])
 
 _status = {}   # device index -> int32[2] tensor
 _debug = False
@@ -80,6 +83,11 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _opt(t):
+    """An optional tensor's address as the plain int the `x.data_ptr()` arguments beside it pass; None is the C-ABI's NULL."""
+    return None if t is None else t.data_ptr()
+
+
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -95,15 +103,15 @@ def _weights(metric, weights, n, device):
     return w
 
 
-FLAG_LOW_LDS = 1
-FLAG_GENERIC = 2      # spd: force the runtime-n one-lane-per-pair kernel
-FLAG_ANY_ORDER = 4    # forward: dispatch without the in-order barrier bit (independent batches of one stream overlap)
-FLAG_COOP = 32        # dims 6, 8: force the sixteen-lanes-per-pair kernel (A/B)
-FLAG_NO_SYMMETRY = 16  # all_pairs_dist(packed=True): evaluate (i, j) and (j, i) separately
-FLAG_SPLIT = 64        # backward, dims 5..8: the split (two-kernel) backward wherever it is built (default: upper model, dims 7, 8)
-FLAG_FUSE = 8         # BatchedForward: up to MAX_FUSED_BATCHES consecutive batches per kernel launch
-FLAG_MERGE_SRC = 128  # model_train_backward(grad_rows=...), dims <= 6: runs of equal source ids inside a wave leave as ONE row
-MAX_FUSED_BATCHES = 32
+FLAG_LOW_LDS = _D["SYMPA_FLAG_LOW_LDS"]
+FLAG_GENERIC = _D["SYMPA_FLAG_GENERIC"]          # spd: force the runtime-n one-lane-per-pair kernel
+FLAG_ANY_ORDER = _D["SYMPA_FLAG_ANY_ORDER"]      # forward: dispatch without the in-order barrier bit (independent batches of one stream overlap)
+FLAG_COOP = _D["SYMPA_FLAG_COOP"]                # dims 6, 8: force the sixteen-lanes-per-pair kernel (A/B)
+FLAG_NO_SYMMETRY = _D["SYMPA_FLAG_NO_SYMMETRY"]  # all_pairs_dist(packed=True): evaluate (i, j) and (j, i) separately
+FLAG_SPLIT = _D["SYMPA_FLAG_SPLIT"]              # backward, dims 5..8: the split (two-kernel) backward wherever it is built (default: upper model, dims 7, 8)
+FLAG_FUSE = _D["SYMPA_FLAG_FUSE"]                # BatchedForward: up to MAX_FUSED_BATCHES consecutive batches per kernel launch
+FLAG_MERGE_SRC = _D["SYMPA_FLAG_MERGE_SRC"]      # model_train_backward(grad_rows=...), dims <= 6: runs of equal source ids inside a wave leave as ONE row
+MAX_FUSED_BATCHES = _D["SYMPA_MAX_FUSED_BATCHES"]
 
 
 def siegel_dist_forward(z1, z2, model="upper", metric="riem", weights=None, eps=None, return_vvd=False, flags=0):
@@ -258,8 +266,8 @@ class BatchedForward:
         if scale is not None:
             self.sc = scale if (scale.device == self.dev and scale.dtype == torch.float64) \
                 else scale.detach().to(self.dev, torch.float64)
-        self.args = (MODEL_IDS[model], METRIC_IDS[metric], None if self.w is None else self.w.data_ptr(),
-                     1e-5 if eps is None else float(eps), None if self.sc is None else self.sc.data_ptr(),
+        self.args = (MODEL_IDS[model], METRIC_IDS[metric], _opt(self.w),
+                     1e-5 if eps is None else float(eps), _opt(self.sc),
                      float(scale_coef))
         self.flags = int(flags)
         self.status = _status_buf(self.dev)
@@ -474,7 +482,7 @@ def model_forward_packed(packed, triplets, metric="riem", weights=None, scale=No
     tp = triplets.data_ptr()
     with torch.cuda.device(dev):
         rc = lib.sympa_model_forward_packed(packed.pack.data_ptr(), packed.bytes, packed.num_rows, n, tp, stride, tp + 8, stride, b,
-                                            mid, METRIC_IDS[metric], None if w is None else w.data_ptr(),
+                                            mid, METRIC_IDS[metric], _opt(w),
                                             1e-5 if eps is None else float(eps), sc_ptr, float(scale_coef), out.data_ptr(),
                                             _status_buf(dev).data_ptr(), 0, torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
@@ -688,10 +696,10 @@ def model_loss_backward(table, triplets, graph_dist, grad_table, loss, model="up
     with torch.cuda.device(dev):
         rc = lib.sympa_model_loss_backward(
             tab.data_ptr(), num_rows, n, tp, stride, tp + 8, stride, gd.data_ptr(), b, MODEL_IDS[model],
-            METRIC_IDS[metric], None if w is None else w.data_ptr(), eps, sc_ptr, float(scale_coef), float(loss_scale),
-            loss.data_ptr(), grad_table.data_ptr(), None if grad_weights is None else grad_weights.data_ptr(),
-            None if grad_scale is None else grad_scale.data_ptr(), None, st.data_ptr(),
-            None if ws is None else ws.data_ptr(), ws_bytes, int(flags), torch.cuda.current_stream(dev).cuda_stream)
+            METRIC_IDS[metric], _opt(w), eps, sc_ptr, float(scale_coef), float(loss_scale),
+            loss.data_ptr(), grad_table.data_ptr(), _opt(grad_weights),
+            _opt(grad_scale), None, st.data_ptr(),
+            _opt(ws), ws_bytes, int(flags), torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
         _lib.check(rc)
     if _debug:
@@ -735,11 +743,11 @@ def model_loss_backward_rows(table, triplets, graph_dist, grad_rows, loss, model
     with torch.cuda.device(dev):
         rc = lib.sympa_model_loss_backward_rows(
             tab.data_ptr(), num_rows, n, tp, stride, tp + 8, stride, gd.data_ptr(), b, MODEL_IDS[model],
-            METRIC_IDS[metric], None if w is None else w.data_ptr(), eps, sc_ptr, float(scale_coef), float(loss_scale),
+            METRIC_IDS[metric], _opt(w), eps, sc_ptr, float(scale_coef), float(loss_scale),
             loss.data_ptr(), grad_rows.data_ptr(), grad_rows.data_ptr() + b * rowbytes,
-            None if grad_weights is None else grad_weights.data_ptr(),
-            None if grad_scale is None else grad_scale.data_ptr(), None, st.data_ptr(),
-            None if ws is None else ws.data_ptr(), ws_bytes, int(flags), torch.cuda.current_stream(dev).cuda_stream)
+            _opt(grad_weights),
+            _opt(grad_scale), None, st.data_ptr(),
+            _opt(ws), ws_bytes, int(flags), torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
         _lib.check(rc)
     if _debug:
@@ -822,8 +830,8 @@ def projx(z, model, eps=None, counter=None):
     word = _outside_word(z.shape[2], z.device)
     with torch.cuda.device(z.device):
         rc = lib.sympa_projx(z.data_ptr(), z.shape[0], z.shape[2], MODEL_IDS[model], eps, out.data_ptr(),
-                             None if counter is None else counter.data_ptr(), st.data_ptr(),
-                             None if word is None else word.data_ptr(), _stream())
+                             _opt(counter), st.data_ptr(),
+                             _opt(word), _stream())
     _lib.check(rc)
     return out
 
@@ -837,7 +845,7 @@ def sgd_step_clipped_(param, grad, lr, weight_decay=0.0, clip_sqnorm=None, max_n
         raise ValueError("param and grad must be contiguous float64 tensors")
     with torch.cuda.device(param.device):
         rc = lib.sympa_sgd_step_clipped(param.data_ptr(), grad.data_ptr(), param.numel(), float(lr), float(weight_decay),
-                                        None if clip_sqnorm is None else clip_sqnorm.data_ptr(),
+                                        _opt(clip_sqnorm),
                                         float(max_norm) if max_norm is not None else 0.0, _stream())
     _lib.check(rc)
     return param
@@ -871,16 +879,16 @@ def rsgd_step_(table, grad, model, lr, weight_decay=0.0, eps=None, counter=None,
     eps = EPS[torch.float64] if eps is None else float(eps)
     st = _status_buf(table.device)
     word = _outside_word(table.shape[2], table.device)
-    wp = None if word is None else word.data_ptr()
+    wp = _opt(word)
     with torch.cuda.device(table.device):
         if clip_sqnorm is not None:
             rc = lib.sympa_rsgd_step_clipped(table.data_ptr(), grad.data_ptr(), table.shape[0], table.shape[2],
                                              MODEL_IDS[model], float(lr), float(weight_decay), eps,
                                              clip_sqnorm.data_ptr(), float(max_norm),
-                                             None if counter is None else counter.data_ptr(), st.data_ptr(), wp, _stream())
+                                             _opt(counter), st.data_ptr(), wp, _stream())
         else:
             rc = lib.sympa_rsgd_step(table.data_ptr(), grad.data_ptr(), table.shape[0], table.shape[2], MODEL_IDS[model],
-                                     float(lr), float(weight_decay), eps, None if counter is None else counter.data_ptr(),
+                                     float(lr), float(weight_decay), eps, _opt(counter),
                                      st.data_ptr(), wp, _stream())
     _lib.check(rc)
     return table
@@ -907,7 +915,7 @@ def radam_step_(table, grad, exp_avg, exp_avg_sq, bias_pows, model, lr, betas=(0
         rc = lib.sympa_radam_step(table.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), table.shape[0],
                                   table.shape[2], MODEL_IDS[model], float(lr), float(betas[0]), float(betas[1]), float(eps_adam),
                                   float(weight_decay), bias_pows.data_ptr(), eps,
-                                  None if counter is None else counter.data_ptr(), st.data_ptr(), _stream())
+                                  _opt(counter), st.data_ptr(), _stream())
     _lib.check(rc)
     return table
 
@@ -949,13 +957,13 @@ def model_train_backward(table, triplets, graph_dist, batch, loss, model="upper"
     with torch.cuda.device(dev):
         rc = lib.sympa_model_train_backward(
             table.data_ptr(), table.shape[0], n, tp, stride, tp + 8, stride, graph_dist.data_ptr(), int(batch),
-            None if step_counter is None else step_counter.data_ptr(), MODEL_IDS[model], METRIC_IDS[metric],
-            None if w is None else w.data_ptr(), 1e-5 if eps is None else float(eps), sc_ptr, float(scale_coef),
-            float(loss_scale), loss.data_ptr(), None if grad_table is None else grad_table.data_ptr(),
-            None if grad_rows is None else grad_rows.data_ptr(), None if grad_weights is None else grad_weights.data_ptr(),
-            None if grad_scale is None else grad_scale.data_ptr(),
-            None if wave_partials is None else wave_partials.data_ptr(), st.data_ptr(),
-            None if ws is None else ws.data_ptr(), ws_bytes, int(flags), _stream())
+            _opt(step_counter), MODEL_IDS[model], METRIC_IDS[metric],
+            _opt(w), 1e-5 if eps is None else float(eps), sc_ptr, float(scale_coef),
+            float(loss_scale), loss.data_ptr(), _opt(grad_table),
+            _opt(grad_rows), _opt(grad_weights),
+            _opt(grad_scale),
+            _opt(wave_partials), st.data_ptr(),
+            _opt(ws), ws_bytes, int(flags), _stream())
     if rc != 0:
         _lib.check(rc)
     return loss
@@ -1008,12 +1016,12 @@ def segment_sum_rows_(grad_table, rows, order, rowptr, alpha=1.0, accumulate=Fal
     with torch.cuda.device(grad_table.device):
         rc = lib.sympa_segment_sum_rows(
             rows.data_ptr(), order.data_ptr(), rowptr.data_ptr(), num_rows, rowd, order.shape[-1],
-            None if step_counter is None else step_counter.data_ptr(), float(alpha), 1 if accumulate else 0,
-            grad_table.data_ptr(), None if wave_partials is None else wave_partials.data_ptr(), int(num_waves),
+            _opt(step_counter), float(alpha), 1 if accumulate else 0,
+            grad_table.data_ptr(), _opt(wave_partials), int(num_waves),
             int(partial_stride), nw,
-            None if loss is None else loss.data_ptr(), None if grad_scale is None else grad_scale.data_ptr(),
-            None if grad_weights is None else grad_weights.data_ptr(),
-            None if sq_partials is None else sq_partials.data_ptr(), _stream())
+            _opt(loss), _opt(grad_scale),
+            _opt(grad_weights),
+            _opt(sq_partials), _stream())
     _lib.check(rc)
     return grad_table
 
@@ -1156,8 +1164,8 @@ def all_pairs_dist(table, model="upper", metric="riem", weights=None, scale=None
         with torch.cuda.device(tab.device):
             rc = lib.sympa_all_pairs_dist_packed(tab.data_ptr(), num_rows, n, int(row_begin), row_count,
                                                  MODEL_IDS[model], METRIC_IDS[metric],
-                                                 None if w is None else w.data_ptr(), eps,
-                                                 None if sc is None else sc.data_ptr(), float(scale_coef),
+                                                 _opt(w), eps,
+                                                 _opt(sc), float(scale_coef),
                                                  out.data_ptr(), workspace.data_ptr(),
                                                  workspace.numel() * workspace.element_size(), st.data_ptr(), int(flags),
                                                  _stream())
@@ -1167,8 +1175,8 @@ def all_pairs_dist(table, model="upper", metric="riem", weights=None, scale=None
         return out
     with torch.cuda.device(tab.device):
         rc = lib.sympa_all_pairs_dist(tab.data_ptr(), num_rows, n, int(row_begin), row_count, MODEL_IDS[model],
-                                      METRIC_IDS[metric], None if w is None else w.data_ptr(), eps,
-                                      None if sc is None else sc.data_ptr(), float(scale_coef), out.data_ptr(),
+                                      METRIC_IDS[metric], _opt(w), eps,
+                                      _opt(sc), float(scale_coef), out.data_ptr(),
                                       st.data_ptr(), int(flags), _stream())
     _lib.check(rc)
     if _debug:
@@ -1222,7 +1230,7 @@ def spd_model_forward(table, triplets, scale=None, scale_coef=1.0, out=None, fla
     tp = triplets.data_ptr()
     with torch.cuda.device(tab.device):
         rc = lib.sympa_spd_model_forward(tab.data_ptr(), tab.shape[0], tab.shape[1], tp, stride, tp + 8, stride, b,
-                                         None if sc is None else sc.data_ptr(), float(scale_coef), out.data_ptr(),
+                                         _opt(sc), float(scale_coef), out.data_ptr(),
                                          st.data_ptr(), int(flags), _stream())
     _lib.check(rc)
     if _debug:
@@ -1290,7 +1298,7 @@ def spd_model_forward_packed(packed, triplets, scale=None, scale_coef=1.0, out=N
     tp = triplets.data_ptr()
     with torch.cuda.device(dev):
         rc = lib.sympa_spd_model_forward_packed(packed.pack.data_ptr(), packed.bytes, packed.num_rows, packed.n, tp, stride, tp + 8,
-                                                stride, b, None if sc is None else sc.data_ptr(), float(scale_coef),
+                                                stride, b, _opt(sc), float(scale_coef),
                                                 out.data_ptr(), _status_buf(dev).data_ptr(), 0, _stream())
     _lib.check(rc)
     if _debug:
@@ -1362,11 +1370,11 @@ def spd_backward_rows(x, y, triplets=None, grad_out=None, graph_dist=None, scale
     ws, ws_bytes = _spd_bwd_workspace(lib, b, n, dev, flags, workspace)
     with torch.cuda.device(dev):
         rc = lib.sympa_spd_backward_rows(
-            x.data_ptr(), y.data_ptr(), x.shape[0], n, sp, stride, dp, stride, b, None if sc is None else sc.data_ptr(),
-            float(scale_coef), None if go is None else go.data_ptr(), None if gd is None else gd.data_ptr(),
-            float(loss_scale), None if loss is None else loss.data_ptr(), rows.data_ptr(),
-            rows.data_ptr() + b * n * n * 8, None if grad_scale is None else grad_scale.data_ptr(),
-            None if out is None else out.data_ptr(), st.data_ptr(), None if ws is None else ws.data_ptr(), int(ws_bytes),
+            x.data_ptr(), y.data_ptr(), x.shape[0], n, sp, stride, dp, stride, b, _opt(sc),
+            float(scale_coef), _opt(go), _opt(gd),
+            float(loss_scale), _opt(loss), rows.data_ptr(),
+            rows.data_ptr() + b * n * n * 8, _opt(grad_scale),
+            _opt(out), st.data_ptr(), _opt(ws), int(ws_bytes),
             int(flags), _stream())
     _lib.check(rc)
     if _debug:
@@ -1415,11 +1423,11 @@ def spd_loss_backward(table, triplets, grad_table, grad_out=None, graph_dist=Non
     ws, ws_bytes = _spd_bwd_workspace(lib, b, n, dev, flags, workspace)
     with torch.cuda.device(dev):
         rc = lib.sympa_spd_loss_backward(
-            tab.data_ptr(), tab.shape[0], n, tp, stride, tp + 8, stride, b, None if sc is None else sc.data_ptr(),
-            float(scale_coef), None if go is None else go.data_ptr(), None if gd is None else gd.data_ptr(),
-            float(loss_scale), None if loss is None else loss.data_ptr(), grad_table.data_ptr(),
-            None if grad_scale is None else grad_scale.data_ptr(), None if out is None else out.data_ptr(),
-            st.data_ptr(), None if ws is None else ws.data_ptr(), int(ws_bytes), int(flags), _stream())
+            tab.data_ptr(), tab.shape[0], n, tp, stride, tp + 8, stride, b, _opt(sc),
+            float(scale_coef), _opt(go), _opt(gd),
+            float(loss_scale), _opt(loss), grad_table.data_ptr(),
+            _opt(grad_scale), _opt(out),
+            st.data_ptr(), _opt(ws), int(ws_bytes), int(flags), _stream())
     _lib.check(rc)
     if _debug:
         check_status(dev)
@@ -1471,7 +1479,7 @@ def spd_projx(x, counter=None):
     st = _status_buf(x.device)
     with torch.cuda.device(x.device):
         rc = lib.sympa_spd_projx(x.data_ptr(), x.shape[0], x.shape[1], out.data_ptr(),
-                                 None if counter is None else counter.data_ptr(), st.data_ptr(), _stream())
+                                 _opt(counter), st.data_ptr(), _stream())
     _lib.check(rc)
     return out
 
@@ -1490,7 +1498,7 @@ def spd_rsgd_step_(table, grad, lr, weight_decay=0.0, clip_sqnorm=None, max_norm
     st = _status_buf(table.device)
     with torch.cuda.device(table.device):
         rc = lib.sympa_spd_rsgd_step(table.data_ptr(), grad.data_ptr(), table.shape[0], table.shape[1], float(lr),
-                                     float(weight_decay), None if clip_sqnorm is None else clip_sqnorm.data_ptr(),
+                                     float(weight_decay), _opt(clip_sqnorm),
                                      float(max_norm) if max_norm is not None else 0.0, st.data_ptr(), _stream())
     _lib.check(rc)
     return table
@@ -1515,7 +1523,7 @@ def spd_radam_step_(table, grad, exp_avg, exp_avg_sq, bias_pows, lr, betas=(0.9,
         rc = lib.sympa_spd_radam_step(table.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), table.shape[0],
                                       table.shape[1], float(lr), float(betas[0]), float(betas[1]), float(eps_adam),
                                       float(weight_decay), bias_pows.data_ptr(),
-                                      None if clip_sqnorm is None else clip_sqnorm.data_ptr(),
+                                      _opt(clip_sqnorm),
                                       float(max_norm) if max_norm is not None else 0.0, st.data_ptr(), _stream())
     _lib.check(rc)
     return table
@@ -1524,8 +1532,8 @@ def spd_radam_step_(table, grad, exp_avg, exp_avg_sq, bias_pows, lr, betas=(0.9,
 # ---------------------------------------------------------------------------------------------------
 # Vector models (C-ABI sympa_vector_*): points are rows of `dims` doubles
 # ---------------------------------------------------------------------------------------------------
-VECTOR_MODEL_IDS = {"euclidean": 0, "poincare": 1, "lorentz": 2, "sphere": 3, "prod-hysph": 4, "prod-hyhy": 5, "prod-hyeu": 6,
-                    "prod-sphsph": 7}
+VECTOR_MODEL_IDS = {m: _D["SYMPA_VECTOR_" + m.upper().replace("-", "_")] for m in (
+    "euclidean", "poincare", "lorentz", "sphere", "prod-hysph", "prod-hyhy", "prod-hyeu", "prod-sphsph")}
 VECTOR_MAX_DIMS = 1024
 # factor geometries per model: E, P, L, S; a product splits the row into two halves
 VECTOR_FACTORS = {"euclidean": "E", "poincare": "P", "lorentz": "L", "sphere": "S", "prod-hysph": "PS", "prod-hyhy": "PP",
@@ -1602,7 +1610,7 @@ def vector_model_forward(table, triplets, model, scale=None, scale_coef=1.0, out
     tp = triplets.data_ptr()
     with torch.cuda.device(tab.device):
         rc = lib.sympa_vector_model_forward(tab.data_ptr(), tab.shape[0], tab.shape[1], tp, stride, tp + 8, stride, b,
-                                            VECTOR_MODEL_IDS[model], None if sc is None else sc.data_ptr(), float(scale_coef),
+                                            VECTOR_MODEL_IDS[model], _opt(sc), float(scale_coef),
                                             out.data_ptr(), st.data_ptr(), 0, _stream())
     _lib.check(rc)
     if _debug:
@@ -1630,7 +1638,7 @@ def vector_all_pairs_dist(table, model, scale=None, scale_coef=1.0, row_begin=0,
     st = _status_buf(tab.device)
     with torch.cuda.device(tab.device):
         rc = lib.sympa_vector_all_pairs_dist(tab.data_ptr(), N, tab.shape[1], int(row_begin), int(row_count), VECTOR_MODEL_IDS[model],
-                                             None if sc is None else sc.data_ptr(), float(scale_coef), out.data_ptr(),
+                                             _opt(sc), float(scale_coef), out.data_ptr(),
                                              st.data_ptr(), 0, _stream())
     _lib.check(rc)
     if _debug:
@@ -1676,10 +1684,10 @@ def vector_backward_rows(x, y, model, triplets=None, grad_out=None, graph_dist=N
     with torch.cuda.device(dev):
         rc = lib.sympa_vector_backward_rows(
             x.data_ptr(), y.data_ptr(), x.shape[0], dims, VECTOR_MODEL_IDS[model], sp, stride, dp, stride, b,
-            None if sc is None else sc.data_ptr(), float(scale_coef), None if go is None else go.data_ptr(),
-            None if gd is None else gd.data_ptr(), float(loss_scale), None if loss is None else loss.data_ptr(), rows.data_ptr(),
-            rows.data_ptr() + b * dims * 8, None if grad_scale is None else grad_scale.data_ptr(),
-            None if out is None else out.data_ptr(), st.data_ptr(), 0, _stream())
+            _opt(sc), float(scale_coef), _opt(go),
+            _opt(gd), float(loss_scale), _opt(loss), rows.data_ptr(),
+            rows.data_ptr() + b * dims * 8, _opt(grad_scale),
+            _opt(out), st.data_ptr(), 0, _stream())
     _lib.check(rc)
     if _debug:
         check_status(dev)
@@ -1708,7 +1716,7 @@ def vector_projx(x, model, counter=None):
     st = _status_buf(x.device)
     with torch.cuda.device(x.device):
         rc = lib.sympa_vector_projx(x.data_ptr(), x.shape[0], x.shape[1], VECTOR_MODEL_IDS[model], out.data_ptr(),
-                                    None if counter is None else counter.data_ptr(), st.data_ptr(), _stream())
+                                    _opt(counter), st.data_ptr(), _stream())
     _lib.check(rc)
     return out
 
@@ -1727,9 +1735,9 @@ def vector_rsgd_step_(table, grad, model, lr, weight_decay=0.0, counter=None, cl
     st = _status_buf(table.device)
     with torch.cuda.device(table.device):
         rc = lib.sympa_vector_rsgd_step(table.data_ptr(), grad.data_ptr(), table.shape[0], table.shape[1], VECTOR_MODEL_IDS[model],
-                                        float(lr), float(weight_decay), None if clip_sqnorm is None else clip_sqnorm.data_ptr(),
+                                        float(lr), float(weight_decay), _opt(clip_sqnorm),
                                         float(max_norm) if max_norm is not None else 0.0,
-                                        None if counter is None else counter.data_ptr(), st.data_ptr(), _stream())
+                                        _opt(counter), st.data_ptr(), _stream())
     _lib.check(rc)
     return table
 
@@ -1753,9 +1761,9 @@ def vector_radam_step_(table, grad, exp_avg, exp_avg_sq, bias_pows, model, lr, b
         rc = lib.sympa_vector_radam_step(table.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), table.shape[0],
                                          table.shape[1], VECTOR_MODEL_IDS[model], float(lr), float(betas[0]), float(betas[1]),
                                          float(eps_adam), float(weight_decay), bias_pows.data_ptr(),
-                                         None if clip_sqnorm is None else clip_sqnorm.data_ptr(),
+                                         _opt(clip_sqnorm),
                                          float(max_norm) if max_norm is not None else 0.0,
-                                         None if counter is None else counter.data_ptr(), st.data_ptr(), _stream())
+                                         _opt(counter), st.data_ptr(), _stream())
     _lib.check(rc)
     return table
 
@@ -1763,8 +1771,8 @@ def vector_radam_step_(table, grad, exp_avg, exp_avg_sq, bias_pows, model, lr, b
 # ---------------------------------------------------------------------------------------------------
 # Mean average precision (C-ABI sympa_map_rows; reference sympa/metrics.py:25-63, runner.py:137-154)
 # ---------------------------------------------------------------------------------------------------
-FLAG_FP32_KEYS = 256   # map_rows: round every distance to fp32 before comparing (the reference's float32 matrix)
-MAP_LDS_CAP = 1024     # map_rows: rows with more CSR entries take the workspace kernel (SYMPA_MAP_LDS_CAP)
+FLAG_FP32_KEYS = _D["SYMPA_FLAG_FP32_KEYS"]   # map_rows: round every distance to fp32 before comparing (the reference's float32 matrix)
+MAP_LDS_CAP = _D["SYMPA_MAP_LDS_CAP"]         # map_rows: rows with more CSR entries take the workspace kernel
 
 
 def neighbor_csr(src_dst_ids, graph_distances, num_nodes):

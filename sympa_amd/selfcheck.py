@@ -16,12 +16,15 @@ import torch
 
 from sympa_amd import _lib
 
-SIEGEL_FWD, SIEGEL_BWD, SIEGEL_TABLE, SPD_FWD, SPD_BWD, SPD_TABLE = range(6)
+# the family ids of include/sympa_hip.h (SYMPA_FAMILY_*)
+SIEGEL_FWD, SIEGEL_BWD, SIEGEL_TABLE, SPD_FWD, SPD_BWD, SPD_TABLE = (
+    _lib.DEFINES["SYMPA_FAMILY_" + f] for f in ("SIEGEL_FWD", "SIEGEL_BWD", "SIEGEL_TABLE", "SPD_FWD", "SPD_BWD", "SPD_TABLE"))
 NAMES = ("siegel forward", "siegel backward", "siegel table ops", "spd forward", "spd backward", "spd table ops")
 # dims whose DEFAULT dispatch reaches the layout (csrc dispatchers; include/sympa_hip.h SYMPA_FAMILY_*)
 RANGE = {SIEGEL_FWD: (9, 16), SIEGEL_BWD: (7, 16), SIEGEL_TABLE: (7, 16), SPD_FWD: (6, 16), SPD_BWD: (3, 16),
          SPD_TABLE: (3, 16)}
-MODEL_IDS = {"upper": 0, "bounded": 1, "spd": 0}
+# the header's convention for sympa_set/get_instance_fallback: SYMPA_MODEL_*, "0 for the spd families"
+MODEL_IDS = {"upper": _lib.DEFINES["SYMPA_MODEL_UPPER"], "bounded": _lib.DEFINES["SYMPA_MODEL_BOUNDED"], "spd": 0}
 
 ENABLED = os.environ.get("SYMPA_SELFCHECK", "1") != "0"
 FAILURES = []          # (family name, model, n, device index, detail)

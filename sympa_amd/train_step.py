@@ -412,7 +412,7 @@ class GraphedTrainStep:
             self._body()
         self.key = self._key()
         # the graph writes the gradients through these addresses
-        self.grad_ptrs = [None if p.grad is None else p.grad.data_ptr() for p in self.params]
+        self.grad_ptrs = [ops._opt(p.grad) for p in self.params]
         self.state_ptrs = self._state_ptrs()
 
     def _ready(self):
@@ -423,7 +423,7 @@ class GraphedTrainStep:
         if self.graph is None or self._key() != self.key:
             self._capture()          # learning rate / weight decay / clip norm / betas of any group changed (end of burn-in)
         for p, ptr in zip(self.params, self.grad_ptrs):
-            if (None if p.grad is None else p.grad.data_ptr()) != ptr:
+            if ops._opt(p.grad) != ptr:
                 # e.g. zero_grad(set_to_none=True) between replays: the graph would write freed memory
                 raise RuntimeError("a parameter's .grad was replaced since the step was captured; keep the gradient "
                                    "tensors (zero_grad(set_to_none=False)) or build a new GraphedTrainStep")

@@ -196,3 +196,112 @@ def test_the_instance_list_is_the_cross_product_of_every_family():
     assert len(instances) == 84 and len({tuple(d) + (src,) for _, src, d in instances}) == 84
     assert {"siegel_bwd_coop_upper_9_dense", "siegel_bwd_half_bounded_8_scatter", "siegel_bwd_split_spectral_upper_5",
             "siegel_bwd_split_gradient_bounded_6_dense", "siegel_bwd_n7_dual_scatter"} <= {name for name, _, _ in instances}
+
+
+# ---- the ctypes prototypes and the constants are read from the header (sympa_amd/_lib.py::parse_header) --------------------
+
+_TYPE_NAME = {getattr(ctypes, n): n for n in ("c_int", "c_int64", "c_double", "c_void_p", "c_char_p")}
+
+
+def _type_names(fn):
+    return [_TYPE_NAME[fn.restype], [_TYPE_NAME[t] for t in fn.argtypes or ()]]
+
+
+def test_prototypes_equal_the_recorded_hand_written_table():
+    """tests/golden/abi_prototypes.json was recorded from the hand-written argtypes table this binding used to carry (never from
+    the parser): every entry it names is still declared and keeps exactly those types on the loaded handle.  An ABI-stability
+    lock for the 71 entries of that day, not a mirror: later entries need not be added."""
+    import json
+    recorded = json.load(open(os.path.join(ROOT, "tests", "golden", "abi_prototypes.json")))
+    assert len(recorded) == 71
+    lib = _lib.load()
+    for name, types in recorded.items():
+        assert name in _lib.SYMBOLS, name
+        assert _type_names(getattr(lib, name)) == types, name
+
+
+def test_arity_counted_by_an_independent_reader():
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "sympa_hip.h")).read(), flags=re.S)
+    args = dict(re.findall(r"\b(sympa_[a-z_0-9]+)\s*\(([^)]*)\)", text))
+    assert sorted(args) == declared_symbols() and len(args) >= 71
+    lib = _lib.load()
+    for name, a in args.items():
+        fn = getattr(lib, name)
+        assert len(fn.argtypes or ()) == (0 if a.strip() == "void" else a.count(",") + 1), name
+        assert fn.restype in (ctypes.c_int, ctypes.c_int64, ctypes.c_char_p), name   # set for every entry (the default is c_int)
+        assert _lib.PROTOTYPES[name][0] is fn.restype, name
+
+
+def test_one_prototype_of_every_type_shape():
+    lib = _lib.load()
+    P, L, I, D = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double
+    assert not lib.sympa_version.argtypes and lib.sympa_version.restype is ctypes.c_char_p
+    assert list(lib.sympa_table_pack_bytes.argtypes) == [L, I, I] and lib.sympa_table_pack_bytes.restype is L
+    batches = lib.sympa_model_forward_batches.argtypes
+    assert batches[3] is P and batches[13] is P and batches[16] is P    # const int64_t* const*, double* const*, void* const*
+    assert list(batches) == [P, L, I, P, L, P, I, I, I, P, D, P, D, P, P, I, P, I]
+    fused = list(lib.sympa_radam_step_fused.argtypes)
+    assert len(fused) == 33 and fused[8:15] == [D] * 7
+    assert fused == [P, P, P, P, P, L, I, I, D, D, D, D, D, D, D, I, P, P, P, P, P, P, P, P, I, P, L, P, I, P, P, P, P]
+    assert lib.sympa_radam_step_fused.restype is I
+
+
+@pytest.mark.parametrize("text", [
+    "int sympa_x(float a);",                        # a by-value type outside the table
+    "int sympa_x(struct s a);",
+    "double* sympa_x(void);",                       # a pointer return other than const char*
+    "int sympa_x(int a, double b",                  # cut off before );
+    "int sympa_y(int a);\nint sympa_x(int64_t b, const double* c",
+])
+def test_the_parser_refuses_what_it_cannot_type(text):
+    with pytest.raises(_lib.SympaHipError, match="sympa_x"):
+        _lib.parse_header(text)
+
+
+def test_the_parser_reads_declarations_and_defines_and_skips_comments():
+    protos, defines = _lib.parse_header(
+        "/* int sympa_old(float a); sympa_model_forward(...) */\n#ifndef SYMPA_HIP_H\n#define SYMPA_HIP_H\n"
+        "#define SYMPA_A 7 /* seven,\n  sympa_b(  */\n#define SYMPA_ERR (-2)\n"
+        "const char* sympa_v(void);\nint64_t sympa_w(const int64_t* const* a, int b,\n   double c, int64_t d, void* const* e);\n#endif\n")
+    assert list(protos.items()) == [("sympa_v", (ctypes.c_char_p, [])), ("sympa_w", (ctypes.c_int64, [
+        ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int64, ctypes.c_void_p]))]
+    assert defines == {"SYMPA_A": 7, "SYMPA_ERR": -2}
+
+
+def test_a_missing_header_fails_loudly(monkeypatch):
+    monkeypatch.setattr(_lib, "HEADER_PATH", "/nonexistent/sympa_hip.h")
+    with pytest.raises(_lib.SympaHipError, match="sympa_hip.h not found"):
+        _lib.read_header()
+
+
+def test_constants_keep_their_values():
+    from sympa_amd import ops, selfcheck
+    assert (ops.FLAG_LOW_LDS, ops.FLAG_GENERIC, ops.FLAG_ANY_ORDER, ops.FLAG_FUSE, ops.FLAG_NO_SYMMETRY, ops.FLAG_COOP, ops.FLAG_SPLIT,
+            ops.FLAG_MERGE_SRC, ops.FLAG_FP32_KEYS) == (1, 2, 4, 8, 16, 32, 64, 128, 256)
+    assert (ops.ST_NOT_PD, ops.ST_NONFINITE, ops.ST_BAD_INDEX, ops.ST_NO_CONVERGENCE) == (1, 2, 4, 8)
+    assert ops.MAX_FUSED_BATCHES == 32 and ops.MAP_LDS_CAP == 1024
+    assert ops.MODEL_IDS == {"upper": 0, "bounded": 1, "dual": 2}
+    assert ops.METRIC_IDS == {"riem": 0, "fone": 1, "finf": 2, "fmin": 3, "wsum": 4}
+    assert ops.VECTOR_MODEL_IDS == {"euclidean": 0, "poincare": 1, "lorentz": 2, "sphere": 3, "prod-hysph": 4, "prod-hyhy": 5,
+                                    "prod-hyeu": 6, "prod-sphsph": 7}
+    assert (selfcheck.SIEGEL_FWD, selfcheck.SIEGEL_BWD, selfcheck.SIEGEL_TABLE, selfcheck.SPD_FWD, selfcheck.SPD_BWD,
+            selfcheck.SPD_TABLE) == (0, 1, 2, 3, 4, 5)
+    assert selfcheck.MODEL_IDS == {"upper": 0, "bounded": 1, "spd": 0}
+    assert all(type(v) is int for v in _lib.DEFINES.values()) and "SYMPA_HIP_H" not in _lib.DEFINES
+
+
+def test_bind_types_a_second_handle_and_names_a_missing_symbol():
+    lib = _lib.load()
+    other = ctypes.CDLL(_lib.LIB_PATH)
+    assert other is not lib and other.sympa_model_forward.argtypes is None
+    assert _lib.bind(other) is other
+    for name in _lib.SYMBOLS:
+        assert _type_names(getattr(other, name)) == _type_names(getattr(lib, name)), name
+
+    class Partial:
+        pass
+    for name in _lib.SYMBOLS:
+        if name != "sympa_map_rows":
+            setattr(Partial, name, staticmethod(lambda: None))
+    with pytest.raises(_lib.SympaHipError, match="does not export sympa_map_rows"):
+        _lib.bind(Partial())

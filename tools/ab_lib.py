@@ -6,7 +6,7 @@ replays each graph once; prints median / min / p90 us per launch and checks that
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from sympa_amd import data
+from sympa_amd import _lib, data
 
 paths = [a for a in sys.argv[1:] if not a.startswith("--")]
 streams = 4 if "--overlap" in sys.argv else 1       # --overlap: launches alternate over 4 streams, minimum-LDS kernel form
@@ -20,11 +20,7 @@ batches = [data.sample_pairs(nodes, batch, j).to(dev) for j in range(nb)]
 status = torch.zeros(2, dtype=torch.int32, device=dev)
 variants = []
 for p in paths:
-    lib = ctypes.CDLL(os.path.abspath(p))
-    fn = lib.sympa_model_forward
-    fn.restype = ctypes.c_int
-    V, I64, I, D = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double
-    fn.argtypes = [V, I64, I, V, I64, V, I64, I64, I, I, V, D, V, D, V, V, I, V]
+    fn = _lib.bind(ctypes.CDLL(os.path.abspath(p))).sympa_model_forward
     outs = [torch.empty(batch, dtype=torch.float64, device=dev) for _ in range(nb)]
 
     def launch(i, fn=fn, outs=outs):

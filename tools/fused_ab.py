@@ -4,7 +4,7 @@ launch) across BUILDS of the library on one device:   python tools/fused_ab.py a
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from sympa_amd import data
+from sympa_amd import _lib, data
 
 paths = [a for a in sys.argv[1:] if not a.startswith("--") and a.endswith(".so")]
 K = int(sys.argv[sys.argv.index("--k") + 1]) if "--k" in sys.argv else 20
@@ -16,13 +16,10 @@ table = data.trained_like_table(nodes, n, model=model).to(dev)
 scale = torch.ones(1, dtype=torch.float64, device=dev)
 batches = [data.sample_pairs(nodes, batch, j).to(dev) for j in range(nb)]
 status = torch.zeros(4, dtype=torch.int32, device=dev)
-V, I64, I, D = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double
+V, I64 = ctypes.c_void_p, ctypes.c_int64
 variants = []
 for p in paths:
-    lib = ctypes.CDLL(os.path.abspath(p))
-    fn = lib.sympa_model_forward_batches
-    fn.restype = I
-    fn.argtypes = [V, I64, I, V, I64, V, I, I, I, V, D, V, D, V, V, I, V, I]
+    fn = _lib.bind(ctypes.CDLL(os.path.abspath(p))).sympa_model_forward_batches
     outs = [torch.empty(batch, dtype=torch.float64, device=dev) for _ in range(nb)]
     trip = (V * K)(*[batches[i % nb].data_ptr() for i in range(K)])
     bb = (I64 * K)(*[batch] * K)

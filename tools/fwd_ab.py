@@ -6,7 +6,7 @@ first build's."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from sympa_amd import data
+from sympa_amd import _lib, data
 
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 flags = int(sys.argv[sys.argv.index("--flags") + 1], 0) if "--flags" in sys.argv else 0
@@ -22,12 +22,8 @@ nb = 4
 batches = [data.sample_pairs(nodes, batch, j).to(dev) for j in range(nb)]
 status = torch.zeros(2, dtype=torch.int32, device=dev)
 variants = []
-V, I64, I, D = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double
 for p in paths:
-    lib = ctypes.CDLL(os.path.abspath(p))
-    fn = lib.sympa_model_forward
-    fn.restype = ctypes.c_int
-    fn.argtypes = [V, I64, I, V, I64, V, I64, I64, I, I, V, D, V, D, V, V, I, V]
+    fn = _lib.bind(ctypes.CDLL(os.path.abspath(p))).sympa_model_forward
     outs = [torch.empty(batch, dtype=torch.float64, device=dev) for _ in range(nb)]
 
     def launch(i, fn=fn, outs=outs):

@@ -5,7 +5,7 @@ HIP events around groups of 8 sequential calls; outputs compared with the first 
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from sympa_amd import data
+from sympa_amd import _lib, data
 
 args = sys.argv[1:]
 model, n, nodes, batch = args[0], int(args[1]), int(args[2]), int(args[3])
@@ -18,15 +18,9 @@ nb = 4
 batches = [data.sample_pairs(nodes, batch, j).to(dev) for j in range(nb)]
 status = torch.zeros(2, dtype=torch.int32, device=dev)
 variants = []
-V, I64, I, D = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double
 for p in paths:
-    lib = ctypes.CDLL(os.path.abspath(p))
-    lib.sympa_table_pack_bytes.restype = I64
-    lib.sympa_table_pack_bytes.argtypes = [I64, I, I]
-    lib.sympa_table_pack.argtypes = [V, I64, I, I, V, I64, V, V]
+    lib = _lib.bind(ctypes.CDLL(os.path.abspath(p)))
     fn = lib.sympa_model_forward_packed
-    fn.restype = I
-    fn.argtypes = [V, I64, I64, I, V, I64, V, I64, I64, I, I, V, D, V, D, V, V, I, V]
     pb = lib.sympa_table_pack_bytes(nodes, n, mid)
     pack = torch.empty(pb, dtype=torch.uint8, device=dev)
     assert lib.sympa_table_pack(table.data_ptr(), nodes, n, mid, pack.data_ptr(), pb, status.data_ptr(), torch.cuda.current_stream().cuda_stream) == 0
