@@ -321,6 +321,33 @@ int sympa_scatter_add_rows(const double* rows, const int64_t* idx, int64_t idx_s
 int sympa_scatter_add_flat_rows(const double* rows, const int64_t* idx, int64_t idx_stride, int64_t count, int row_doubles,
                                 int64_t num_rows, double alpha, double* grad_table, int32_t* status, void* stream);
 
+/* ---- the differentiable vector-valued distance ------------------------------------------------------------
+ * v [b, n], ascending: the vector every metric of the library reduces (the reference's intermediate,
+ * siegel_manifold.py:41-72; compact_dual.py:60 for model = DUAL).  With these entries ANY function of v -- an lp norm, a
+ * learned weighting, a Weyl-chamber regulariser -- is ordinary code on the caller's side: the forward hands v out, the
+ * backward takes dLoss/dv [b, n] (on the ascending v) and returns the gradients of the points.  Models UPPER, BOUNDED, DUAL;
+ * n in [1, SYMPA_MAX_DIMS_BACKWARD]; one pair per lane (dims 1..6 in registers, dims 7..16 rolled loops over per-lane scratch).
+ * The model scale is NOT part of these entries (callers multiply v by it).  `flags` is reserved and must be 0.  b == 0: no-op.
+ *
+ * sympa_model_vvd_forward: the gathered forward of sympa_model_forward (siegel_manifold.py:41-72 over model.py:16-30) with the
+ * vector written instead of a metric of it: row i of vvd_out is bit for bit what sympa_siegel_dist_fwd(..., vvd_out) writes for
+ * the points table[src[i]], table[dst[i]].  A pair with an out-of-range index sets SYMPA_ST_BAD_INDEX and gets a NaN row. */
+int sympa_model_vvd_forward(const double* table, int64_t num_rows, int n, const int64_t* src, int64_t src_stride,
+                            const int64_t* dst, int64_t dst_stride, int64_t b, int model, double eps, double* vvd_out,
+                            int32_t* status, int flags, void* stream);
+/* Backward of the vector-valued distance for pre-gathered points (what autograd computes through siegel_manifold.py:41-72 up to
+ * the sorted v):  grad_v [b, n] in;  grad_z1, grad_z2 [b, 2, n, n] written (symmetric matrices);  vvd_out [b, n] or NULL receives
+ * v again (from the backward's own eigen-decomposition: equal to the forward's to rounding, not bit for bit).  src == dst gives
+ * v = 0 and a zero gradient; the cut locus of the dual model gives NaN and SYMPA_ST_NONFINITE. */
+int sympa_siegel_vvd_bwd(const double* z1, const double* z2, const double* grad_v, int64_t b, int n, int model, double eps,
+                         double* grad_z1, double* grad_z2, double* vvd_out, int32_t* status, int flags, void* stream);
+/* The same through the table gather (siegel_manifold.py:41-72 under model.py:16-30): the two gradient rows of every pair are
+ * ACCUMULATED into grad_table [num_rows, 2, n, n] (fp64 atomics; zero it first).  A pair with an out-of-range index sets
+ * SYMPA_ST_BAD_INDEX, contributes nothing and gets a NaN row in vvd_out. */
+int sympa_model_vvd_backward(const double* table, int64_t num_rows, int n, const int64_t* src, int64_t src_stride,
+                             const int64_t* dst, int64_t dst_stride, int64_t b, int model, double eps, const double* grad_v,
+                             double* grad_table, double* vvd_out, int32_t* status, int flags, void* stream);
+
 /* ---- optimiser-side manifold operations over table rows (one [2,n,n] point per row) --------------------
  * egrad2rgrad: UpperHalfManifold.egrad2rgrad (sympa/manifolds/upper_half.py:25-40, Y G Y on both planes) /
  *              BoundedDomainManifold.egrad2rgrad (sympa/manifolds/bounded_domain.py:41-53, A G A, A = I - conj(Z) Z).

@@ -68,6 +68,52 @@ def model_forward(table, triplets, model, metric, weights=None, scale=None, scal
     return ops.model_forward(table, triplets, model, metric, weights, scale, scale_coef)
 
 
+class _SiegelVvdFn(torch.autograd.Function):
+    """The ascending vector-valued distance v [b, n] of pre-gathered points with the analytic backward (sympa_siegel_vvd_bwd)."""
+
+    @staticmethod
+    def forward(ctx, z1, z2, model):
+        ctx.save_for_backward(z1, z2)
+        ctx.model = model
+        return ops.siegel_dist_forward(z1, z2, model, "riem", return_vvd=True)[1]
+
+    @staticmethod
+    def backward(ctx, grad_v):
+        z1, z2 = ctx.saved_tensors
+        g1, g2 = ops.siegel_vvd_backward(z1, z2, grad_v, ctx.model)
+        return (g1 if ctx.needs_input_grad[0] else None, g2 if ctx.needs_input_grad[1] else None, None)
+
+
+def siegel_vvd(z1, z2, model):
+    """v [b, n], ascending; differentiable with respect to both points.  Any function of v is a metric, e.g. an lp norm:
+        v = siegel_vvd(z1, z2, "upper");  d = v.pow(3).sum(-1).pow(1 / 3)"""
+    if _needs_grad(z1, z2):
+        return _SiegelVvdFn.apply(z1, z2, model)
+    return ops.siegel_dist_forward(z1, z2, model, "riem", return_vvd=True)[1]
+
+
+class _ModelVvdFn(torch.autograd.Function):
+    """v [b, n] of the pairs of a triplet batch gathered from the table (sympa_model_vvd_forward) with the scatter-add backward
+    (sympa_model_vvd_backward) into the dense [N,2,n,n] table gradient."""
+
+    @staticmethod
+    def forward(ctx, table, triplets, model):
+        ctx.save_for_backward(table, triplets)
+        ctx.model = model
+        return ops.model_vvd_forward(table, triplets, model)
+
+    @staticmethod
+    def backward(ctx, grad_v):
+        table, triplets = ctx.saved_tensors
+        return ops.model_vvd_backward(table, triplets, grad_v, ctx.model), None, None
+
+
+def model_vvd(table, triplets, model):
+    if _needs_grad(table):
+        return _ModelVvdFn.apply(table, triplets, model)
+    return ops.model_vvd_forward(table, triplets, model)
+
+
 class _SpdDistFn(torch.autograd.Function):
     """SymmetricPositiveDefinite.dist(x, y) with the analytic backward (sympa_spd_backward_rows)."""
 

@@ -113,6 +113,8 @@ bool instance_fallback(int family, int model, int n);
 char* last_error_buffer();
 int fail(int code, const char* msg);
 int validate(const DistArgs& a, int model, int n);
+// siegel_dist.hip: the forward dispatch behind sympa_siegel_dist_fwd / sympa_model_forward (a.out and, optionally, a.vvd are written)
+int launch_dist(const DistArgs& a, int n, int model, void* stream);
 
 // siegel_coop.hip: 9 <= n <= 16, sixteen lanes per pair
 int launch_siegel_coop(const DistArgs& a, int n, int model, hipStream_t s);

@@ -248,6 +248,9 @@ int launch_multi(const double* table, int64_t num_rows, int n, const int64_t* co
 }  // namespace
 
 namespace sympa_hip {
+// the forward dispatch for entries defined in other units (siegel_vvd_bwd.hip: sympa_model_vvd_forward)
+int launch_dist(const DistArgs& a, int n, int model, void* stream) { return launch(a, n, model, stream); }
+
 namespace {
 std::atomic<unsigned char> g_instance_fallback[SYMPA_NUM_FAMILIES][2][SYMPA_MAX_DIMS_GENERIC + 1];
 }

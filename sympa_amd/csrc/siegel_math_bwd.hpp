@@ -496,12 +496,11 @@ SYMPA_UNROLL
 //   phi_i = go * d out / d lambda_i,   philam_i = phi_i lambda_i,   gw[k] += go * d out / d w_k  (wsum)
 // (shared by the one-pair-per-lane adjoint below and the sixteen-lanes-per-pair one, siegel_coop_bwd.hpp)
 // ---------------------------------------------------------------------------------------------
+// v_i(lambda_i) and dv_i / dlambda_i of every eigenvalue, in the order the eigenvalues come in (not sorted)
 template <int N, int MODEL>
-SYMPA_HD double spectral_adjoint(const double (&lam_in)[N], int metric, const double* __restrict__ w, double inv_eps,
-                                 double go, double (&phi)[N], double (&philam)[N], double (&gw)[N], bool& finite) {
+SYMPA_HD void spectral_values(const double (&lam_in)[N], double inv_eps, double (&vv)[N], double (&dv)[N], bool& finite) {
     const double scale = (MODEL == MODEL_UPPER) ? 0.25 : 1.0;
-    double vv[N], dv[N], lam[N];
-    int rank[N];
+    double lam[N];
     finite = true;
 SYMPA_UNROLL
     for (int i = 0; i < N; ++i) {
@@ -536,13 +535,27 @@ SYMPA_UNROLL
         vv[i] = d_log1p(u);
         dv[i] = deriv;
     }
+}
+
+// ascending rank, ties broken by index
+template <int N>
+SYMPA_HD void ascending_rank(const double (&vv)[N], int (&rank)[N]) {
 SYMPA_UNROLL
-    for (int i = 0; i < N; ++i) {   // ascending rank, ties broken by index
+    for (int i = 0; i < N; ++i) {
         int r = 0;
 SYMPA_UNROLL
         for (int j = 0; j < N; ++j) r += (vv[j] < vv[i] || (vv[j] == vv[i] && j < i)) ? 1 : 0;
         rank[i] = r;
     }
+}
+
+template <int N, int MODEL>
+SYMPA_HD double spectral_adjoint(const double (&lam_in)[N], int metric, const double* __restrict__ w, double inv_eps,
+                                 double go, double (&phi)[N], double (&philam)[N], double (&gw)[N], bool& finite) {
+    double vv[N], dv[N];
+    int rank[N];
+    spectral_values<N, MODEL>(lam_in, inv_eps, vv, dv, finite);
+    ascending_rank<N>(vv, rank);
     double out = 0.0, vbar[N];
     if (metric == METRIC_RIEM) {
 SYMPA_UNROLL
@@ -574,6 +587,27 @@ SYMPA_UNROLL
     for (int i = 0; i < N; ++i) { phi[i] = go * vbar[i] * dv[i]; philam[i] = phi[i] * lam_in[i]; }
 
     return out;
+}
+
+// The same stage for a cotangent on the vector-valued distance itself: gv[k] = dLoss / dv_(k), v_(0) <= ... <= v_(N-1) (the
+// ascending order sympa_siegel_dist_fwd writes), so vbar_i = gv[rank_i] -- no metric, no relu, no go, no gw.  The ascending v
+// goes to v_out (may be null); every entry is NaN where the pair is not finite (NaN / Inf input, the dual cut locus).
+template <int N, int MODEL>
+SYMPA_HD void spectral_adjoint_vvd(const double (&lam_in)[N], const double* __restrict__ gv, double inv_eps, double (&phi)[N],
+                                   double (&philam)[N], double* __restrict__ v_out, bool& finite) {
+    double vv[N], dv[N];
+    int rank[N];
+    spectral_values<N, MODEL>(lam_in, inv_eps, vv, dv, finite);
+    ascending_rank<N>(vv, rank);
+SYMPA_UNROLL
+    for (int i = 0; i < N; ++i) {
+        phi[i] = gv[rank[i]] * dv[i];
+        philam[i] = phi[i] * lam_in[i];
+    }
+    if (v_out != nullptr) {
+SYMPA_UNROLL
+        for (int i = 0; i < N; ++i) v_out[rank[i]] = finite ? vv[i] : __builtin_nan("");
+    }
 }
 
 // S = L^-T M L^-1 for symmetric M (full matrix in, upper triangle i <= j of S out, in m)
@@ -710,10 +744,11 @@ struct KeepFactors {
     SYMPA_HD void operator()(int, T&) const {}
 };
 
-template <int N, int MODEL, class Park = KeepFactors, class Unpark = KeepFactors>
-SYMPA_HD double pair_backward(const CMat<N>& z1, const CMat<N>& z2, int metric, const double* __restrict__ w,
-                              double inv_eps, double go, CMat<N>& g1, CMat<N>& g2, double (&gw)[N], int& status,
-                              Park&& park = Park(), Unpark&& unpark = Unpark()) {
+// The adjoint around the spectral stage: spectral(lambda, phi, philam, finite) fills the spectral weights from the eigenvalues of H
+// and returns the pair's value (pair_backward: the metric; pair_backward_vvd: nothing, the vector goes out on its own).
+template <int N, int MODEL, class Spectral, class Park, class Unpark>
+SYMPA_HD double pair_backward_core(const CMat<N>& z1, const CMat<N>& z2, Spectral&& spectral, CMat<N>& g1, CMat<N>& g2, int& status,
+                                   Park&& park, Unpark&& unpark) {
     constexpr bool CPLX = (MODEL != MODEL_UPPER);     // complex Hermitian factor: bounded and dual
     Tri<N, CPLX> l1, l2;
     CMat<N> e;
@@ -765,7 +800,7 @@ SYMPA_UNROLL
 
     double phi[N], philam[N];
     bool finite;
-    double out = spectral_adjoint<N, MODEL>(h.d, metric, w, inv_eps, go, phi, philam, gw, finite);
+    double out = spectral(h.d, phi, philam, finite);
 
     if constexpr (MODEL == MODEL_UPPER && N <= 4) {
         upper_adjoint_tail_lean<N>(e, v, phi, philam, l1, l2, unpark, g1, g2);
@@ -849,6 +884,33 @@ SYMPA_UNROLL
     if (!conv) status |= ST_NO_CONVERGENCE;
     if (!d_finite(out)) status |= ST_NONFINITE;
     return out;
+}
+
+template <int N, int MODEL, class Park = KeepFactors, class Unpark = KeepFactors>
+SYMPA_HD double pair_backward(const CMat<N>& z1, const CMat<N>& z2, int metric, const double* __restrict__ w,
+                              double inv_eps, double go, CMat<N>& g1, CMat<N>& g2, double (&gw)[N], int& status,
+                              Park&& park = Park(), Unpark&& unpark = Unpark()) {
+    return pair_backward_core<N, MODEL>(
+        z1, z2,
+        [&](const double (&lam)[N], double (&phi)[N], double (&philam)[N], bool& finite) {
+            return spectral_adjoint<N, MODEL>(lam, metric, w, inv_eps, go, phi, philam, gw, finite);
+        },
+        g1, g2, status, park, unpark);
+}
+
+// One pair, cotangent on the vector-valued distance: gv[N] = dLoss / dv on the ASCENDING v (any function of v is then ordinary
+// code on the caller's side).  g1, g2: the symmetric matrix gradients; v_out (may be null): the ascending v.  src == dst gives
+// lambda = 0, weight 0 and a zero gradient; the dual cut locus gives NaN gradients, a NaN v and ST_NONFINITE.
+template <int N, int MODEL, class Park = KeepFactors, class Unpark = KeepFactors>
+SYMPA_HD void pair_backward_vvd(const CMat<N>& z1, const CMat<N>& z2, const double* __restrict__ gv, double inv_eps, CMat<N>& g1,
+                                CMat<N>& g2, double* __restrict__ v_out, int& status, Park&& park = Park(), Unpark&& unpark = Unpark()) {
+    pair_backward_core<N, MODEL>(
+        z1, z2,
+        [&](const double (&lam)[N], double (&phi)[N], double (&philam)[N], bool& finite) {
+            spectral_adjoint_vvd<N, MODEL>(lam, gv, inv_eps, phi, philam, v_out, finite);
+            return finite ? 0.0 : __builtin_nan("");
+        },
+        g1, g2, status, park, unpark);
 }
 
 }  // namespace sympa

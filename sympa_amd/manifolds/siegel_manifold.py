@@ -63,8 +63,12 @@ class SiegelManifold(Manifold, ABC):
         return siegel_dist(z1, z2, self.model_name, self.metric.kind.value, self._metric_weights())
 
     def vvd(self, z1, z2):
-        """Ascending vector-valued distance v (the reference's intermediate, siegel_manifold.py:69-70)."""
-        return ops.siegel_dist_forward(z1, z2, self.model_name, "riem", return_vvd=True)[1]
+        """Ascending vector-valued distance v [b, n] (the reference's intermediate, siegel_manifold.py:69-70); differentiable
+        when an input requires grad (sympa_siegel_vvd_bwd).  Every metric is a function of v, so a custom one is ordinary torch code
+        on it, e.g. an lp norm:
+            v = manifold.vvd(z1, z2);  d = v.pow(p).sum(-1).pow(1 / p)"""
+        from sympa_amd.autograd import siegel_vvd
+        return siegel_vvd(z1, z2, self.model_name)
 
     # ------------------------------------------------------------------ geoopt surface
     def retr(self, x, u):  # siegel_manifold.py:74-87

@@ -133,6 +133,20 @@ class Model(nn.Module):
                 return ops.model_forward_packed(pk, input_triplet, metric_name, weights, scale, self.scale_coef)
         return ops.model_forward(table, input_triplet, model_name, metric_name, weights, scale, self.scale_coef)
 
+    def forward_vvd(self, input_triplet):
+        """input_triplet: int64 [b, 2|3] -> [b, n]: the ascending vector-valued distance v of every pair times
+        max(scale / scale_coef, 0.1) (the factor forward() applies, model.py:40-41; here in torch, so the scale's gradient comes from
+        autograd).  Differentiable with respect to the table (sympa_model_vvd_backward scatters into the dense table gradient) and
+        the scale.  Every built-in metric is a function of v; a custom one is ordinary torch code on it, e.g. an lp norm:
+            v = model.forward_vvd(triplets);  dist = v.pow(3).sum(-1).pow(1 / 3)
+        Siegel models only (upper, bounded, dual)."""
+        name = self.manifold.model_name
+        if name not in ops.MODEL_IDS:
+            raise NotImplementedError(f"forward_vvd: the vector-valued distance exists for the Siegel models "
+                                      f"({', '.join(ops.MODEL_IDS)}), not for '{name}'")
+        v = sa.model_vvd(self.embeddings.embeds, input_triplet, name)
+        return v * (self.scale * (1.0 / self.scale_coef)).clamp_min(0.1)       # (the kernels' scale * (1 / scale_coef))
+
     def packed_table(self):
         """The ops.PackedTable of this model's embedding table (dims 5..8 of the Siegel models, n in ops.SPD_PACKED_DIMS of the spd
         model, on the GPU; None elsewhere, with `model.use_packed = False` or SYMPA_NO_PACKED=1, or while the self-check has demoted

@@ -662,6 +662,108 @@ def model_backward(table, triplets, grad_out, model="upper", metric="riem", weig
     return grad_table, gw, gs
 
 
+def _vvd_table_args(table, triplets):
+    """The checks of the table entries of the vector-valued distance -> (contiguous detached table, triplets, row stride)."""
+    _need_gpu(table, "table"); _need_gpu(triplets, "triplets")
+    if table.dtype != torch.float64:
+        raise TypeError("table must be float64")
+    if table.dim() != 4 or table.shape[1] != 2 or table.shape[2] != table.shape[3]:
+        raise ValueError(f"table must be [N,2,n,n], got {tuple(table.shape)}")
+    if triplets.dtype != torch.int64 or triplets.dim() != 2 or triplets.shape[1] < 2:
+        raise TypeError("triplets must be an int64 [b, >=2] tensor (src, dst[, graph_distance])")
+    tab = table.detach()
+    if not tab.is_contiguous():
+        tab = tab.contiguous()
+    if triplets.stride(1) != 1:
+        triplets = triplets.contiguous()
+    stride = triplets.stride(0) if triplets.shape[0] > 1 else triplets.shape[1]
+    return tab, triplets, stride
+
+
+def model_vvd_forward(table, triplets, model="upper", eps=None):
+    """The ascending vector-valued distance v [b, n] of the pairs (table[triplets[:, 0]], table[triplets[:, 1]]), gathered inside
+    the kernel (C-ABI sympa_model_vvd_forward; the reference's intermediate, siegel_manifold.py:41-72 over model.py:16-30).  Row
+    i is bit for bit siegel_dist_forward(..., return_vvd=True) on the gathered points.  No scale: callers multiply."""
+    lib = _lib.load()
+    tab, triplets, stride = _vvd_table_args(table, triplets)
+    num_rows, _, n, _ = tab.shape
+    b = triplets.shape[0]
+    vvd = torch.empty(b, n, dtype=torch.float64, device=tab.device)
+    if b == 0:
+        return vvd
+    _gate(_sc.SIEGEL_FWD, model, n, tab.device)
+    eps = EPS[torch.float64] if eps is None else float(eps)
+    st = _status_buf(tab.device)
+    tp = triplets.data_ptr()
+    with torch.cuda.device(tab.device):
+        rc = lib.sympa_model_vvd_forward(_ptr(tab), num_rows, n, tp, stride, tp + 8, stride, b, MODEL_IDS[model], eps, _ptr(vvd),
+                                         _ptr(st), 0, _stream())
+    _lib.check(rc)
+    if _debug:
+        check_status(tab.device)
+    return vvd
+
+
+def siegel_vvd_backward(z1, z2, grad_v, model="upper", eps=None, return_vvd=False):
+    """Backward of the vector-valued distance for pre-gathered points (C-ABI sympa_siegel_vvd_bwd): grad_v [b, n] on the ascending
+    v -> (grad_z1, grad_z2) [b,2,n,n] (and v [b, n] from the backward's own eigen-decomposition with return_vvd)."""
+    lib = _lib.load()
+    _need_gpu(z1, "z1"); _need_gpu(z2, "z2"); _need_gpu(grad_v, "grad_v")
+    if z1.dtype != torch.float64 or z2.dtype != torch.float64:
+        raise TypeError("points must be float64 (reference default dtype, config.py:17-18)")
+    if z1.shape != z2.shape or z1.dim() != 4 or z1.shape[1] != 2 or z1.shape[2] != z1.shape[3]:
+        raise ValueError(f"expected two [b,2,n,n] tensors, got {tuple(z1.shape)} and {tuple(z2.shape)}")
+    z1 = z1.detach().contiguous()
+    z2 = z2.detach().contiguous()
+    b, _, n, _ = z1.shape
+    if tuple(grad_v.shape) != (b, n):
+        raise ValueError(f"grad_v must be [{b}, {n}], got {tuple(grad_v.shape)}")
+    gv = grad_v.detach().to(torch.float64).contiguous()
+    g1 = torch.empty_like(z1)
+    g2 = torch.empty_like(z2)
+    vvd = torch.empty(b, n, dtype=torch.float64, device=z1.device) if return_vvd else None
+    eps = EPS[torch.float64] if eps is None else float(eps)
+    st = _status_buf(z1.device)
+    if b > 0:
+        with torch.cuda.device(z1.device):
+            rc = lib.sympa_siegel_vvd_bwd(_ptr(z1), _ptr(z2), _ptr(gv), b, n, MODEL_IDS[model], eps, _ptr(g1), _ptr(g2), _ptr(vvd),
+                                          _ptr(st), 0, _stream())
+        _lib.check(rc)
+    if _debug:
+        check_status(z1.device)
+    return (g1, g2, vvd) if return_vvd else (g1, g2)
+
+
+def model_vvd_backward(table, triplets, grad_v, model="upper", eps=None, grad_table=None, return_vvd=False):
+    """Backward of model_vvd_forward (C-ABI sympa_model_vvd_backward): the two gradient rows of every pair are scatter-added (fp64
+    atomics) into a dense [N,2,n,n] gradient (created zeroed unless `grad_table` is given, in which case it accumulates).
+    Returns grad_table (and v [b, n] with return_vvd)."""
+    lib = _lib.load()
+    _need_gpu(grad_v, "grad_v")
+    tab, triplets, stride = _vvd_table_args(table, triplets)
+    num_rows, _, n, _ = tab.shape
+    b = triplets.shape[0]
+    if tuple(grad_v.shape) != (b, n):
+        raise ValueError(f"grad_v must be [{b}, {n}], got {tuple(grad_v.shape)}")
+    gv = grad_v.detach().to(torch.float64).contiguous()
+    if grad_table is None:
+        grad_table = torch.zeros_like(tab)
+    elif grad_table.shape != tab.shape or grad_table.dtype != torch.float64 or not grad_table.is_contiguous() or not grad_table.is_cuda:
+        raise ValueError("grad_table must be a contiguous float64 device tensor of the table's shape")
+    vvd = torch.empty(b, n, dtype=torch.float64, device=tab.device) if return_vvd else None
+    eps = EPS[torch.float64] if eps is None else float(eps)
+    st = _status_buf(tab.device)
+    if b > 0:
+        tp = triplets.data_ptr()
+        with torch.cuda.device(tab.device):
+            rc = lib.sympa_model_vvd_backward(_ptr(tab), num_rows, n, tp, stride, tp + 8, stride, b, MODEL_IDS[model], eps,
+                                              _ptr(gv), _ptr(grad_table), _ptr(vvd), _ptr(st), 0, _stream())
+        _lib.check(rc)
+    if _debug:
+        check_status(tab.device)
+    return (grad_table, vvd) if return_vvd else grad_table
+
+
 def model_loss_backward(table, triplets, graph_dist, grad_table, loss, model="upper", metric="riem", weights=None,
                         grad_weights=None, scale=None, grad_scale=None, scale_coef=1.0, loss_scale=1.0, eps=None, flags=0,
                         workspace=None):
