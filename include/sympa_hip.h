@@ -560,6 +560,40 @@ int sympa_spd_radam_step(double* table, const double* grad, double* exp_avg, dou
                          double lr, double beta1, double beta2, double eps_adam, double weight_decay, const double* bias_pows,
                          const double* total_sqnorm, double max_norm, int32_t* status, void* stream);
 
+/* ---- spd: the differentiable vector-valued distance ------------------------------------------
+ * v [b, n] = log(lam_j) ASCENDING, lam = the eigenvalues of x^-1 y, evaluated as log(1 + a_j), a = the eigenvalues of
+ * L^-1 (y - x) L^-T, x = L L^T.  v is SIGNED (lam_j < 1 gives v_j < 0), unlike the Siegel v above; the affine-invariant distance
+ * is ||v||_2, the Finsler distances sum_j |v_j| and max_j |v_j|.  With these entries any function of v is ordinary code on the
+ * caller's side: the forward hands v out, the backward takes dLoss/dv [b, n] (on the ascending v).  n in [1, 16]; flags: 0 or
+ * SYMPA_FLAG_GENERIC (the one-pair-per-lane kernels at every n).  The model scale is NOT part of these entries.  b == 0: no-op.
+ * Null required pointers, b < 0, other flags: SYMPA_ERR_BAD_ARG; n outside the range: SYMPA_ERR_UNSUPPORTED_DIMS.
+ * Status bits as for sympa_spd_dist_fwd / sympa_spd_backward_rows; the row of v of a pair whose eigenvalues came out NaN (flagged
+ * SYMPA_ST_NOT_PD / SYMPA_ST_NONFINITE) is unspecified.
+ * Ties: eigenvalues that agree exactly are ranked in index order and their eigenvectors are whatever the QL returns; the backward
+ * is well defined there whenever grad_v is constant across the tied block.  x == y gives v = 0 and exact zero gradients.
+ *
+ * sympa_spd_vvd_fwd: pre-gathered points x, y [b, n, n] (upper triangle read).  n <= 5 one lane per pair, n = 6..16 sixteen lanes
+ * per pair (csrc/spd_vvd_kernel.hpp: spd_vvd_coop_fwd_kernel, the rounds of the distance kernel, rows of v staged through the LDS). */
+int sympa_spd_vvd_fwd(const double* x, const double* y, int64_t b, int n, double* vvd_out, int32_t* status, int flags, void* stream);
+/* The same for pair i = (table[src[i]], table[dst[i]]), table [num_rows, n, n]: row i is bit for bit what sympa_spd_vvd_fwd writes
+ * for the gathered points.  A pair with an out-of-range index sets SYMPA_ST_BAD_INDEX and gets a NaN row. */
+int sympa_spd_model_vvd_forward(const double* table, int64_t num_rows, int n, const int64_t* src, int64_t src_stride,
+                                const int64_t* dst, int64_t dst_stride, int64_t b, double* vvd_out, int32_t* status, int flags,
+                                void* stream);
+/* Backward for pre-gathered points:  grad_v [b, n] in;  grad_x, grad_y [b, n, n] written (symmetric),
+ *   grad_y =  sym(L^-T V diag(grad_v[rank(k)] / (1 + a_k)) V^T L^-1),   grad_x = -sym(L^-T V diag(grad_v[rank(k)]) V^T L^-1);
+ * vvd_out [b, n] or NULL receives v again (from the backward's own eigen-decomposition: equal to the forward's to rounding).
+ * n <= 2 one lane per pair (Rayleigh-refined eigenvalues), n = 3..16 sixteen lanes per pair (spd_vvd_coop_bwd_kernel: the
+ * one-kernel form of sympa_spd_backward_rows with SYMPA_FLAG_COOP, a cotangent row per pair in place of log(1 + a_k) / dist). */
+int sympa_spd_vvd_bwd(const double* x, const double* y, const double* grad_v, int64_t b, int n, double* grad_x, double* grad_y,
+                      double* vvd_out, int32_t* status, int flags, void* stream);
+/* The same through the table gather: the two gradient rows of every pair are ACCUMULATED into grad_table [num_rows, n, n] (fp64
+ * atomics; zero it first; n >= 3 without SYMPA_FLAG_GENERIC: consecutive lanes on consecutive doubles).  A pair with an out-of-range
+ * index sets SYMPA_ST_BAD_INDEX, contributes nothing and gets a NaN row in vvd_out (or NULL). */
+int sympa_spd_model_vvd_backward(const double* table, int64_t num_rows, int n, const int64_t* src, int64_t src_stride,
+                                 const int64_t* dst, int64_t dst_stride, int64_t b, const double* grad_v, double* grad_table,
+                                 double* vvd_out, int32_t* status, int flags, void* stream);
+
 /* ---- Vector models (manifolds "euclidean", "poincare", "lorentz", "sphere", "prod-hysph", "prod-hyhy", "prod-hyeu",
  * "prod-sphsph": geoopt constructors behind ManifoldFactory, sympa/embeddings.py:130-158, and VectorEmbeddings,
  * sympa/embeddings.py:82-90).  geoopt is not in the reference tree: PARITY UNPINNED like the spd entries; the definitions are

@@ -167,6 +167,51 @@ def spd_model_forward(table, triplets, scale=None, scale_coef=1.0):
     return ops.spd_model_forward(table, triplets, scale, scale_coef)
 
 
+class _SpdVvdFn(torch.autograd.Function):
+    """The spd model's vector-valued distance v [b, n] (ascending, signed) of pre-gathered points with the analytic backward
+    (sympa_spd_vvd_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, y):
+        ctx.save_for_backward(x, y)
+        return ops.spd_vvd_forward(x, y)
+
+    @staticmethod
+    def backward(ctx, grad_v):
+        x, y = ctx.saved_tensors
+        gx, gy = ops.spd_vvd_backward(x, y, grad_v)
+        return (gx if ctx.needs_input_grad[0] else None, gy if ctx.needs_input_grad[1] else None)
+
+
+def spd_vvd(x, y):
+    """v [b, n] = log of the eigenvalues of x^-1 y, ascending; differentiable with respect to both points.  Any function of v is a
+    metric:  v.norm(dim=-1) is the affine-invariant distance, v.abs().sum(-1) and v.abs().amax(-1) the Finsler distances."""
+    if _needs_grad(x, y):
+        return _SpdVvdFn.apply(x, y)
+    return ops.spd_vvd_forward(x, y)
+
+
+class _SpdModelVvdFn(torch.autograd.Function):
+    """v [b, n] of the pairs of a triplet batch gathered from the spd table (sympa_spd_model_vvd_forward) with the scatter-add
+    backward (sympa_spd_model_vvd_backward) into the dense [N, n, n] table gradient."""
+
+    @staticmethod
+    def forward(ctx, table, triplets):
+        ctx.save_for_backward(table, triplets)
+        return ops.spd_model_vvd_forward(table, triplets)
+
+    @staticmethod
+    def backward(ctx, grad_v):
+        table, triplets = ctx.saved_tensors
+        return ops.spd_model_vvd_backward(table, triplets, grad_v), None
+
+
+def spd_model_vvd(table, triplets):
+    if _needs_grad(table):
+        return _SpdModelVvdFn.apply(table, triplets)
+    return ops.spd_model_vvd_forward(table, triplets)
+
+
 class _VectorDistFn(torch.autograd.Function):
     """dist(x, y) of a vector model on [b, dims] rows with the analytic backward (sympa_vector_backward_rows)."""
 

@@ -223,4 +223,21 @@ SYMPA_HD double spd_pair_distance(SpdWork& w, const double* __restrict__ px, con
     return out;
 }
 
+// Position of a[k] in the stable ascending order of a[0 .. n): the number of m with (a[m], m) < (a[k], k).  Equal values get
+// distinct ranks; n compares per call, no sort.  (NaN compares false everywhere: the ranks are then not a permutation, which only
+// a pair already flagged ST_NONFINITE / ST_NOT_PD can meet.)
+SYMPA_HD int spd_rank(const double* a, int n, int k) {
+    int r = 0;
+    for (int m = 0; m < n; ++m) r += (a[m] < a[k] || (a[m] == a[k] && m < k)) ? 1 : 0;
+    return r;
+}
+
+// The vector-valued distance of one pair: v_out[0 .. n) = log(1 + a_k) in ascending order, signed, a = the
+// eigenvalues of A = L^-1 (y - x) L^-T -- spd_pair_distance leaves them in w.d.  Same status bits.
+SYMPA_HD void spd_pair_vvd(SpdWork& w, const double* __restrict__ px, const double* __restrict__ py, int n,
+                           double* __restrict__ v_out, int& status) {
+    spd_pair_distance(w, px, py, n, status);
+    for (int k = 0; k < n; ++k) v_out[spd_rank(w.d, n, k)] = d_log1p_signed(w.d[k]);
+}
+
 }  // namespace sympa

@@ -301,6 +301,72 @@ SYMPA_HD double spd_pair_backward(SpdBwdWork& w, const double* __restrict__ px, 
     return dist;
 }
 
+// One pair, backward of the vector-valued distance:  v_j = log(1 + a_j) ascending (signed), a = the
+// eigenvalues of A as above;  with a cotangent gv on the ascending v,
+//   gy =  sym(L^-T V diag(gv[rank(k)] / (1 + a_k)) V^T L^-1),   gx = -sym(L^-T V diag(gv[rank(k)]) V^T L^-1),
+//   v_out[rank(k)] = log(1 + a_k)   (v_out may be null)
+// -- spd_pair_backward with the weights log(1 + a_k) / dist replaced by the cotangent's.  Same Rayleigh-quotient refinement, same
+// status bits.  Ties: where eigenvalues agree exactly the eigenvectors of the block are whatever the QL returns and the stable
+// rank assigns the block's cotangents in index order; the result is well defined whenever gv is constant across the block (then
+// sum_k gv V_k V_k^T over the block is the block's projector times gv).  x == y (A = 0 exactly, every eigenvalue tied at 0): v = 0
+// and, like dist there, the zero subgradient -- exact zeros.
+SYMPA_HD void spd_pair_backward_vvd(SpdBwdWork& w, const double* __restrict__ px, const double* __restrict__ py, int n,
+                                    const double* __restrict__ gv, double* __restrict__ gx, double* __restrict__ gy,
+                                    double* __restrict__ v_out, int& status) {
+    bool ok = spd_cholesky(px, n, w.l, w.rd);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) w.a[i * n + j] = sym_at(py, n, i, j) - sym_at(px, n, i, j);
+    spd_congruence_inv(w.a, w.l, w.rd, n);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < i; ++j) { const double t = 0.5 * (w.a[i * n + j] + w.a[j * n + i]); w.a[i * n + j] = t; w.a[j * n + i] = t; }
+    for (int k = 0; k < n * n; ++k) w.p[k] = w.a[k];
+    const bool conv = spd_eigh_ql(w.a, w.v, w.lam, w.f, n);
+    for (int c = 0; c < n; ++c) {
+        double acc2 = 0.0;
+        for (int i = 0; i < n; ++i) {
+            double t = 0.0;
+            for (int k = 0; k < n; ++k) t += w.p[i * n + k] * w.v[k * n + c];
+            acc2 += w.v[i * n + c] * t;
+        }
+        w.lam[c] = acc2;
+    }
+    bool same = true, fin = true;
+    for (int k = 0; k < n; ++k) {
+        ok = ok && (w.lam[k] > -1.0);
+        same = same && (w.lam[k] == 0.0);
+        const double lg = d_log1p_signed(w.lam[k]);
+        fin = fin && d_finite(lg);
+        const int rk = spd_rank(w.lam, n, k);
+        if (v_out != nullptr) v_out[rk] = lg;
+        w.f[k] = gv[rk];
+    }
+    if (same)
+        for (int k = 0; k < n; ++k) w.f[k] = 0.0;
+    for (int i = 0; i < n; ++i)
+        for (int j = i; j < n; ++j) {
+            double t = 0.0;
+            for (int k = 0; k < n; ++k) t += w.v[i * n + k] * (w.f[k] * d_rcp(1.0 + w.lam[k])) * w.v[j * n + k];
+            w.p[i * n + j] = t;
+            w.p[j * n + i] = t;
+        }
+    spd_congruence_inv_t(w.p, w.l, w.rd, n);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) gy[i * n + j] = 0.5 * (w.p[i * n + j] + w.p[j * n + i]);
+    for (int i = 0; i < n; ++i)
+        for (int j = i; j < n; ++j) {
+            double t = 0.0;
+            for (int k = 0; k < n; ++k) t += w.v[i * n + k] * w.f[k] * w.v[j * n + k];
+            w.p[i * n + j] = -t;
+            w.p[j * n + i] = -t;
+        }
+    spd_congruence_inv_t(w.p, w.l, w.rd, n);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) gx[i * n + j] = 0.5 * (w.p[i * n + j] + w.p[j * n + i]);
+    if (!ok) status |= ST_NOT_PD;
+    if (!conv) status |= ST_NO_CONVERGENCE;
+    if (!fin) status |= ST_NONFINITE;
+}
+
 // ---- rows of the table -------------------------------------------------------------------------------------------
 struct SpdRowWork {
     double x[SPD_MAX_N * SPD_MAX_N], u[SPD_MAX_N * SPD_MAX_N], t[SPD_MAX_N * SPD_MAX_N], l[SPD_MAX_N * SPD_MAX_N];

@@ -128,7 +128,8 @@ class ManifoldFactory:
     out_of_scope = set()       # every manifold name of the reference is built
 
     @classmethod
-    def get_manifold(cls, manifold_name, metric_name, dims):
+    def get_manifold(cls, manifold_name, metric_name, dims, spd_metric=None):
+        """spd_metric: the `finsler` of the spd manifold (None, "riem", "fone", "finf"); metric_name is ignored for spd."""
         if manifold_name in cls.out_of_scope:
             raise NotImplementedError(
                 f"manifold '{manifold_name}' is outside the MI355X hot path (SURVEY section 2: its "
@@ -136,6 +137,6 @@ class ManifoldFactory:
         if manifold_name in cls.vector_manifolds:
             return get_vector_manifold(manifold_name, dims)
         if manifold_name == "spd":      # embeddings.py:142
-            return SymmetricPositiveDefinite()
+            return SymmetricPositiveDefinite(finsler=spd_metric)
         manifold = cls.sympa_manifolds[manifold_name]
         return manifold(dims=dims, metric=MetricType.from_str(metric_name))

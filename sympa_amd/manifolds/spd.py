@@ -30,6 +30,22 @@ def torch_radam_row(manifold, x, grad, exp_avg, exp_avg_sq, bias_pows, lr, betas
     return y, _sym(mt), s1
 
 
+FINSLER_KINDS = ("riem", "fone", "finf")
+
+
+def spd_metric(v, kind):
+    """A distance from the vector-valued distance v [..., n] of the spd model (SymmetricPositiveDefinite.vvd; signed,
+    v_j = log lam_j):  riem = sqrt(sum v^2) (the affine-invariant distance),  fone = sum |v_j|,  finf = max |v_j|  (the Finsler
+    distances of the symmetric space).  Ordinary torch code: differentiable through v."""
+    if kind == "riem":
+        return v.pow(2).sum(-1).sqrt()
+    if kind == "fone":
+        return v.abs().sum(-1)
+    if kind == "finf":
+        return v.abs().amax(-1)
+    raise ValueError(f"spd_metric: kind must be one of {FINSLER_KINDS}, got {kind!r}")
+
+
 class SymmetricPositiveDefinite(Manifold):
     name = "SymmetricPositiveDefinite"
     ndim = 2
@@ -37,16 +53,26 @@ class SymmetricPositiveDefinite(Manifold):
     __scaling__ = Manifold.__scaling__.copy()
     model_name = "spd"
 
-    def __init__(self, default_metric="AIM"):
+    def __init__(self, default_metric="AIM", finsler=None):
         super().__init__()
         if str(default_metric).upper() not in ("AIM", "SPDMETRIC.AIM"):
             raise NotImplementedError("only geoopt's default affine-invariant metric (AIM) is built")
+        if finsler is not None and finsler not in FINSLER_KINDS:
+            raise ValueError(f"finsler must be None or one of {FINSLER_KINDS}, got {finsler!r}")
+        self.finsler = finsler
         self.projected_points = 0
 
-    def dist(self, x, y, *, keepdim=False):
-        """|| log(x^-1/2 y x^-1/2) ||_F  (geoopt SymmetricPositiveDefinite.dist, AIM); differentiable."""
+    def vvd(self, x, y):
+        """[b, n]: the vector-valued distance, log of the eigenvalues of x^-1 y, ascending and signed; differentiable with respect
+        to both points (HIP kernels forward and backward)."""
         from sympa_amd import autograd as sa
-        d = sa.spd_dist(x, y)
+        return sa.spd_vvd(x, y)
+
+    def dist(self, x, y, *, keepdim=False):
+        """|| log(x^-1/2 y x^-1/2) ||_F  (geoopt SymmetricPositiveDefinite.dist, AIM); differentiable.  With finsler = "fone" /
+        "finf": spd_metric(self.vvd(x, y), finsler)."""
+        from sympa_amd import autograd as sa
+        d = spd_metric(self.vvd(x, y), self.finsler) if self.finsler in ("fone", "finf") else sa.spd_dist(x, y)
         return d.unsqueeze(-1).unsqueeze(-1) if keepdim else d
 
     def egrad2rgrad(self, x, u):

@@ -12,6 +12,7 @@ from sympa_amd import autograd as sa
 from sympa_amd import ops
 from sympa_amd.embeddings import EmbeddingsFactory, ManifoldFactory
 from sympa_amd.manifolds.metrics import MetricType
+from sympa_amd.manifolds.spd import spd_metric
 
 
 # forward() under no_grad takes the packed path (two launches) from this many pairs per call on
@@ -64,7 +65,7 @@ class Model(nn.Module):
     def __init__(self, args):
         super().__init__()
         self.manifold = ManifoldFactory.get_manifold(manifold_name=args.manifold, metric_name=args.metric,
-                                                     dims=args.dims)
+                                                     dims=args.dims, spd_metric=getattr(args, "spd_metric", None))
         self.embeddings = EmbeddingsFactory.get_embeddings(args.manifold, args.num_points, args.dims,
                                                            self.manifold)
         self.scale_coef = args.scale_coef
@@ -112,6 +113,9 @@ class Model(nn.Module):
         if model_name == "spd" or (metric_name is None and model_name in ops.VECTOR_MODEL_IDS):
             if model_name != "spd":
                 return sa.vector_model_forward(table, input_triplet, model_name, scale, self.scale_coef)
+            kind = self._spd_finsler()
+            if kind is not None:            # a Finsler distance: ordinary torch code on the vector-valued distance
+                return spd_metric(self.forward_vvd(input_triplet), kind)
             if not (torch.is_grad_enabled() and (table.requires_grad or scale.requires_grad)) and \
                     input_triplet.shape[0] >= PACKED_MIN_PAIRS:
                 pk = self.packed_table()            # no autograd graph to build: the packed table once its version is seen twice
@@ -139,13 +143,33 @@ class Model(nn.Module):
         autograd).  Differentiable with respect to the table (sympa_model_vvd_backward scatters into the dense table gradient) and
         the scale.  Every built-in metric is a function of v; a custom one is ordinary torch code on it, e.g. an lp norm:
             v = model.forward_vvd(triplets);  dist = v.pow(3).sum(-1).pow(1 / 3)
-        Siegel models only (upper, bounded, dual)."""
+        The Siegel models (upper, bounded, dual) and spd, whose v = log of the eigenvalues of x^-1 y is signed (DESIGN.md section 23;
+        sympa_spd_model_vvd_forward / _backward) and exists for a table on the device only."""
         name = self.manifold.model_name
+        if name == "spd":
+            if not self.embeddings.embeds.is_cuda:
+                raise NotImplementedError("forward_vvd: the spd model's vector-valued distance is HIP kernels over the table and is "
+                                          "not built for a table on the host: move the model to the GPU")
+            v = sa.spd_model_vvd(self.embeddings.embeds, input_triplet)
+            return v * (self.scale * (1.0 / self.scale_coef)).clamp_min(0.1)
         if name not in ops.MODEL_IDS:
             raise NotImplementedError(f"forward_vvd: the vector-valued distance exists for the Siegel models "
-                                      f"({', '.join(ops.MODEL_IDS)}), not for '{name}'")
+                                      f"({', '.join(ops.MODEL_IDS)}) and spd, not for '{name}'")
         v = sa.model_vvd(self.embeddings.embeds, input_triplet, name)
         return v * (self.scale * (1.0 / self.scale_coef)).clamp_min(0.1)       # (the kernels' scale * (1 / scale_coef))
+
+    def _spd_finsler(self):
+        """"fone" / "finf" when this is an spd model with a Finsler distance (SymmetricPositiveDefinite(finsler=...)), else None:
+        the distance is then spd_metric(forward_vvd(.), kind) and every path that runs the affine-invariant kernels must refuse."""
+        man = self.manifold
+        kind = getattr(man, "finsler", None) if getattr(man, "model_name", None) == "spd" else None
+        return kind if kind in ("fone", "finf") else None
+
+    def _refuse_finsler(self, what):
+        kind = self._spd_finsler()
+        if kind is not None:
+            raise NotImplementedError(f"{what} runs the affine-invariant distance kernels and is not built for the spd model with "
+                                      f"spd_metric='{kind}': use Model.forward (spd_metric over forward_vvd) in the classic loop")
 
     def packed_table(self):
         """The ops.PackedTable of this model's embedding table (dims 5..8 of the Siegel models, n in ops.SPD_PACKED_DIMS of the spd
@@ -183,6 +207,7 @@ class Model(nn.Module):
         `forward_batches` runs; it keeps the tensors alive and reads table, scale and metric weights through their
         device pointers, so parameter updates in place are seen, while `model.to(...)` needs a new plan."""
         from sympa_amd import ops
+        self._refuse_finsler("prepare_batches / forward_batches / evaluate")
         man = self.manifold
         table = self.embeddings.embeds.data
         batches = list(batches)
@@ -217,6 +242,7 @@ class Model(nn.Module):
         alive; at most 8 plans).  Returns the list of [b_i] outputs, enqueued on the current stream.  With outs=None the
         outputs belong to the cached plan: a second call on the SAME list object writes into the same tensors (clone what
         must survive the next call, or pass `outs`)."""
+        self._refuse_finsler("forward_batches")
         if isinstance(batches, (list, tuple)):
             table = self.embeddings.embeds
             key = (tuple(map(id, batches)), None if outs is None else tuple(map(id, outs)),
@@ -238,6 +264,7 @@ class Model(nn.Module):
         every triplet, the model called once per `batch_size` triplets.  Here the batches are row slices of
         `src_dst_ids` [T, 2|3] handed over as one list; the plan and the [T] output are cached on the model (the
         evaluation split is the same every epoch).  One host sync (the returned float)."""
+        self._refuse_finsler("evaluate")
         ids = src_dst_ids if src_dst_ids.is_contiguous() else src_dst_ids.contiguous()
         total = ids.shape[0]
         if total == 0:
@@ -265,6 +292,7 @@ class Model(nn.Module):
         HIP kernel.  Accumulates into the parameters' .grad exactly like loss.backward() and returns the
         loss as a 1-element device tensor (no host sync); `loss_out` (1-element fp64 device tensor) is zeroed
         (unless zero_loss_out=False: the caller has) and used for it when given (a persistent buffer: fewer graph nodes per step)."""
+        self._refuse_finsler("fused_loss_backward")
         from sympa_amd import ops
         man = self.manifold
         table = self.embeddings.embeds
@@ -343,6 +371,7 @@ class Model(nn.Module):
         """fused_loss_backward with the table gradient left as per-pair rows in `grad_rows` [2b, 2, n, n] (written;
         rows [0, b) belong to the src ids, [b, 2b) to the dst ids) for the touched-row gradient exchange of
         sympa_amd.distributed.GradientExchange; the scale / wsum-weight gradients accumulate into .grad as usual."""
+        self._refuse_finsler("fused_loss_backward_rows")
         from sympa_amd import ops
         man = self.manifold
         table = self.embeddings.embeds
@@ -385,6 +414,7 @@ class Model(nn.Module):
     def distance_matrix(self, row_begin=0, row_count=None):
         """Extension: the N x N matrix Runner.build_distance_matrix (runner.py:142-154) assembles with N
         forward calls, as one launch (or one launch per row block).  Diagonal exactly 0."""
+        self._refuse_finsler("distance_matrix")
         from sympa_amd import ops
         man = self.manifold
         if _is_vector(man):
@@ -417,6 +447,7 @@ class Model(nn.Module):
         [N] AP vector is assembled by an exact all-reduce of zero-padded vectors, so the result does not depend on the world size
         or on the block size.  Reads the table only: forward caches and the packed-table state are untouched.  One host sync
         (the returned float); with return_rows=True returns (mAP, AP [N] fp64 device tensor)."""
+        self._refuse_finsler("mean_average_precision")
         from sympa_amd import distributed as sd
         from sympa_amd import metrics as sm
         if dtype not in (torch.float32, torch.float64):
@@ -475,6 +506,7 @@ class Model(nn.Module):
         With `group` set or a default process group initialised every rank takes its contiguous
         share of the rows and the zero-padded [N] vectors are combined by an exact all-reduce: bitwise the single-process value.
         One host sync (the returned float)."""
+        self._refuse_finsler("evaluate_all_pairs")
         from sympa_amd import distributed as sd
         from sympa_amd.graph import WeightedGraphDistances
         man = self.manifold

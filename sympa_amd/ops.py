@@ -1340,6 +1340,118 @@ def spd_model_forward(table, triplets, scale=None, scale_coef=1.0, out=None, fla
     return out
 
 
+# ---- spd: the differentiable vector-valued distance (C-ABI sympa_spd_vvd_fwd / sympa_spd_model_vvd_forward / sympa_spd_vvd_bwd /
+# sympa_spd_model_vvd_backward).  v [b, n] = log of the eigenvalues of x^-1 y, ascending and signed.
+def _spd_vvd_points(x, y):
+    _need_gpu(x, "x"); _need_gpu(y, "y")
+    if x.dtype != torch.float64 or y.dtype != torch.float64 or x.shape != y.shape or x.dim() != 3 or x.shape[1] != x.shape[2]:
+        raise ValueError(f"expected two float64 [b,n,n] tensors, got {tuple(x.shape)} and {tuple(y.shape)}")
+    return x.detach().contiguous(), y.detach().contiguous()
+
+
+def _spd_vvd_table_args(table, triplets):
+    _need_gpu(table, "table"); _need_gpu(triplets, "triplets")
+    if table.dtype != torch.float64 or table.dim() != 3 or table.shape[1] != table.shape[2]:
+        raise ValueError(f"spd table must be float64 [N,n,n], got {tuple(table.shape)}")
+    if triplets.dtype != torch.int64 or triplets.dim() != 2 or triplets.shape[1] < 2:
+        raise TypeError("triplets must be an int64 [b, >=2] tensor (src, dst[, graph_distance])")
+    tab = table.detach()
+    tab = tab if tab.is_contiguous() else tab.contiguous()
+    if triplets.stride(1) != 1:
+        triplets = triplets.contiguous()
+    stride = triplets.stride(0) if triplets.shape[0] > 1 else triplets.shape[1]
+    return tab, triplets, stride
+
+
+def spd_vvd_forward(x, y, flags=0):
+    """v [b, n] of the pre-gathered pairs x, y [b, n, n] (C-ABI sympa_spd_vvd_fwd).  flags: 0 or FLAG_GENERIC."""
+    lib = _lib.load()
+    x, y = _spd_vvd_points(x, y)
+    b, n, _ = x.shape
+    vvd = torch.empty(b, n, dtype=torch.float64, device=x.device)
+    if b == 0:
+        return vvd
+    st = _status_buf(x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.sympa_spd_vvd_fwd(_ptr(x), _ptr(y), b, n, _ptr(vvd), _ptr(st), int(flags), _stream())
+    _lib.check(rc)
+    if _debug:
+        check_status(x.device)
+    return vvd
+
+
+def spd_model_vvd_forward(table, triplets, flags=0):
+    """v [b, n] of the pairs (table[triplets[:, 0]], table[triplets[:, 1]]), gathered inside the kernel (C-ABI
+    sympa_spd_model_vvd_forward): row i is bit for bit spd_vvd_forward on the gathered points.  No scale: callers multiply."""
+    lib = _lib.load()
+    tab, triplets, stride = _spd_vvd_table_args(table, triplets)
+    num_rows, n, _ = tab.shape
+    b = triplets.shape[0]
+    vvd = torch.empty(b, n, dtype=torch.float64, device=tab.device)
+    if b == 0:
+        return vvd
+    st = _status_buf(tab.device)
+    tp = triplets.data_ptr()
+    with torch.cuda.device(tab.device):
+        rc = lib.sympa_spd_model_vvd_forward(_ptr(tab), num_rows, n, tp, stride, tp + 8, stride, b, _ptr(vvd), _ptr(st), int(flags),
+                                             _stream())
+    _lib.check(rc)
+    if _debug:
+        check_status(tab.device)
+    return vvd
+
+
+def spd_vvd_backward(x, y, grad_v, return_vvd=False, flags=0):
+    """Backward of the vector-valued distance for pre-gathered points (C-ABI sympa_spd_vvd_bwd): grad_v [b, n] on the ascending v
+    -> (grad_x, grad_y) [b, n, n] (and v [b, n] from the backward's own eigen-decomposition with return_vvd)."""
+    lib = _lib.load()
+    _need_gpu(grad_v, "grad_v")
+    x, y = _spd_vvd_points(x, y)
+    b, n, _ = x.shape
+    if tuple(grad_v.shape) != (b, n):
+        raise ValueError(f"grad_v must be [{b}, {n}], got {tuple(grad_v.shape)}")
+    gv = grad_v.detach().to(torch.float64).contiguous()
+    gx, gy = torch.empty_like(x), torch.empty_like(y)
+    vvd = torch.empty(b, n, dtype=torch.float64, device=x.device) if return_vvd else None
+    st = _status_buf(x.device)
+    if b > 0:
+        with torch.cuda.device(x.device):
+            rc = lib.sympa_spd_vvd_bwd(_ptr(x), _ptr(y), _ptr(gv), b, n, _ptr(gx), _ptr(gy), _ptr(vvd), _ptr(st), int(flags), _stream())
+        _lib.check(rc)
+    if _debug:
+        check_status(x.device)
+    return (gx, gy, vvd) if return_vvd else (gx, gy)
+
+
+def spd_model_vvd_backward(table, triplets, grad_v, grad_table=None, return_vvd=False, flags=0):
+    """Backward of spd_model_vvd_forward (C-ABI sympa_spd_model_vvd_backward): the two gradient rows of every pair are scatter-added
+    (fp64 atomics) into a dense [N, n, n] gradient (created zeroed unless `grad_table` is given, in which case it accumulates).
+    Returns grad_table (and v [b, n] with return_vvd)."""
+    lib = _lib.load()
+    _need_gpu(grad_v, "grad_v")
+    tab, triplets, stride = _spd_vvd_table_args(table, triplets)
+    num_rows, n, _ = tab.shape
+    b = triplets.shape[0]
+    if tuple(grad_v.shape) != (b, n):
+        raise ValueError(f"grad_v must be [{b}, {n}], got {tuple(grad_v.shape)}")
+    gv = grad_v.detach().to(torch.float64).contiguous()
+    if grad_table is None:
+        grad_table = torch.zeros_like(tab)
+    elif grad_table.shape != tab.shape or grad_table.dtype != torch.float64 or not grad_table.is_contiguous() or not grad_table.is_cuda:
+        raise ValueError("grad_table must be a contiguous float64 device tensor of the table's shape")
+    vvd = torch.empty(b, n, dtype=torch.float64, device=tab.device) if return_vvd else None
+    st = _status_buf(tab.device)
+    if b > 0:
+        tp = triplets.data_ptr()
+        with torch.cuda.device(tab.device):
+            rc = lib.sympa_spd_model_vvd_backward(_ptr(tab), num_rows, n, tp, stride, tp + 8, stride, b, _ptr(gv), _ptr(grad_table),
+                                                  _ptr(vvd), _ptr(st), int(flags), _stream())
+        _lib.check(rc)
+    if _debug:
+        check_status(tab.device)
+    return (grad_table, vvd) if return_vvd else grad_table
+
+
 class SpdPackedTable(PackedTable):
     """PackedTable of the spd model (C-ABI sympa_spd_table_pack, n = 6..16): per point the n x n image [point's upper triangle |
     unit factor Lh of x = Lh D Lh^T in the strict lower triangle] + D^-1/2, made once per table state -- the pair kernel then

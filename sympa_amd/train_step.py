@@ -82,6 +82,8 @@ class GraphedTrainStep:
             raise NotImplementedError(f"GraphedTrainStep is not built for the vector models ('{model.manifold.model_name}'): run the "
                                       "classic loop -- Model.fused_loss_backward (or forward + loss + backward), then "
                                       "RiemannianSGD.step (DESIGN.md section 19)")
+        if hasattr(model, "_refuse_finsler"):
+            model._refuse_finsler("GraphedTrainStep")      # spd with a Finsler distance: the classic loop only
         self.model, self.opt = model, optimizer
         self.batch_size, self.max_grad_norm = int(batch_size), float(max_grad_norm)
         self.device = torch.device(device)
@@ -533,6 +535,8 @@ class DistributedTrainStep:
         table = model.embeddings.embeds
         if getattr(man, "model_name", None) not in ("upper", "bounded", "dual", "spd"):
             raise NotImplementedError("DistributedTrainStep: the Siegel models and spd")
+        if hasattr(model, "_refuse_finsler"):
+            model._refuse_finsler("DistributedTrainStep")      # spd with a Finsler distance: the classic loop only
         self.spd = man.model_name == "spd"
         if self.spd and mode == "auto":
             # the spd backward scatters a dense gradient and never writes per-pair rows: "auto" must not resolve to "rows"

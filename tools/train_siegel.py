@@ -9,6 +9,7 @@ rewrite of them: SURVEY 8f): graph -> triplets -> Model -> fused training step -
     python tools/train_siegel.py --graph product-cartesian-45500 --dims 8 --sampled-pairs 1048576 --batch_size 262144 --subsample 0.01
     python tools/train_siegel.py --graph grid3d-125 --manifold poincare --optim radam --dims 4
     python tools/train_siegel.py --graph grid3d-125 --manifold spd --optim radam --dims 3
+    python tools/train_siegel.py --graph grid3d-125 --manifold spd --spd-metric fone --dims 3
 
 Per batch it runs exactly two kernels: sympa_model_loss_backward (forward + AverageDistortionLoss + backward +
 scatter, runner.py:101-105) and sympa_rsgd_step (geoopt RiemannianSGD, train.py:66-68), plus the gradient clip
@@ -28,6 +29,7 @@ import torch.distributed as dist  # noqa: E402
 
 from sympa_amd import data, ops  # noqa: E402
 from sympa_amd.distributed import GradientExchange, shard_triplets  # noqa: E402
+from sympa_amd.losses import AverageDistortionLoss  # noqa: E402
 from sympa_amd.data import sort_batches_by_source  # noqa: E402
 from sympa_amd.train_step import batches_want_source_order  # noqa: E402
 from sympa_amd.model import Model  # noqa: E402
@@ -39,6 +41,33 @@ def evaluate(model, ids, gd, batch):
     """Average distortion |d_manifold - d_graph| / d_graph (sympa/metrics.py:21, runner.py:124-135): Model.evaluate hands
     the batches of the split to the fused multi-batch kernel as one list (one C call per evaluation)."""
     return model.evaluate(ids, gd, batch)
+
+
+def finsler_kind(args):
+    """"fone" / "finf" when the run trains the spd model under a Finsler distance (--spd-metric), else None."""
+    kind = getattr(args, "spd_metric", None) or "riem"
+    if kind != "riem" and args.manifold != "spd":
+        raise SystemExit("--spd-metric is the distance of --manifold spd")
+    return kind if kind in ("fone", "finf") else None
+
+
+def finsler_loss_backward(model, ids, gd):
+    """The classic loop's forward + AverageDistortionLoss + backward for the spd model under a Finsler distance: Model.forward is
+    spd_metric over forward_vvd (sympa_spd_model_vvd_forward / _backward), the loss ordinary torch code.  Returns the loss (detached)."""
+    loss = AverageDistortionLoss().calculate_loss(gd, model(ids))
+    loss.backward()
+    return loss.detach()
+
+
+def finsler_evaluate(model, ids, gd, batch):
+    """Average distortion over the triplets through Model.forward, one call per batch (the list kernels run the affine-invariant
+    distance and refuse a Finsler model)."""
+    total = torch.zeros((), dtype=torch.float64, device=gd.device)
+    with torch.no_grad():
+        for s in range(0, ids.shape[0], batch):
+            g = gd[s:s + batch]
+            total += ((model(ids[s:s + batch]) - g).abs() / g).sum()
+    return float(total) / ids.shape[0]
 
 
 def train(args, log=print):
@@ -86,6 +115,10 @@ def train(args, log=print):
     else:
         trip, id2node = data.graph_triplets(graph)
     args.num_points = len(id2node)
+    finsler = finsler_kind(args)
+    if finsler is not None and (world > 1 or args.grad_exchange != "none" or hops is not None):
+        raise SystemExit(f"--spd-metric {finsler}: the classic single-GPU loop over listed triplets only (no gradient exchange, no "
+                         "--sampled-pairs)")
     model = Model(args).to(dev)
     if args.optim == "radam":        # train.py:69-70
         opt = RiemannianAdam(model.parameters(), lr=args.learning_rate * world, eps=1e-7, stabilize=None)
@@ -130,7 +163,8 @@ def train(args, log=print):
     # single GPU: the whole step is one hipGraph replay
     graphed = GraphedTrainStep(model, opt, batch, args.max_grad_norm, dev,
                                deterministic=True if args.deterministic else None, accumulate_loss=True) \
-        if (world == 1 and args.graph_step and args.grad_exchange == "none" and args.manifold not in ops.VECTOR_MODEL_IDS) else None
+        if (world == 1 and args.graph_step and args.grad_exchange == "none" and args.manifold not in ops.VECTOR_MODEL_IDS
+            and finsler is None) else None
     # (the vector models train through the classic loop below: fused loss + backward rows + scatter, clip, then the optimiser's
     # step -- RiemannianSGD or, with --optim radam, RiemannianAdam: one kernel over the table either way)
     if args.manifold in ops.VECTOR_MODEL_IDS and (world > 1 or args.grad_exchange != "none"):
@@ -207,7 +241,10 @@ def train(args, log=print):
                 graphed(b[:, :2].to(torch.int64), b[:, 2].to(torch.float64))        # accumulates into graphed.loss
                 continue
             ids, gd = b[:, :2].to(torch.int64).contiguous(), b[:, 2].to(torch.float64)
-            if ex is None:
+            if finsler is not None:
+                opt.zero_grad(set_to_none=False)
+                loss_sum += finsler_loss_backward(model, ids, gd)
+            elif ex is None:
                 opt.zero_grad(set_to_none=False)
                 loss_sum += model.fused_loss_backward(ids, gd)
             elif ex.mode == "sharded":
@@ -238,7 +275,10 @@ def train(args, log=print):
         if epoch % args.val_every == 0 or epoch == args.epochs:
             torch.cuda.synchronize(dev)
             t_train = time.perf_counter() - t0
-            distortion = model.evaluate_all_pairs(eval_hops) if hops is not None else evaluate(model, ids_all, gd_all, args.batch_size)
+            if finsler is not None:
+                distortion = finsler_evaluate(model, ids_all, gd_all, args.batch_size)
+            else:
+                distortion = model.evaluate_all_pairs(eval_hops) if hops is not None else evaluate(model, ids_all, gd_all, args.batch_size)
             ops.check_status(dev)
             history.append((epoch, float(loss_sum) / max(1, mine.shape[0]), distortion))
             if rank == 0:
@@ -257,6 +297,10 @@ def parser():
                          "(sympa_amd.graph.WeightedGraphDistances), otherwise hop counts; --sampled-pairs works with both")
     ap.add_argument("--manifold", default="upper")
     ap.add_argument("--metric", default="riem")
+    ap.add_argument("--spd-metric", dest="spd_metric", default="riem", choices=["riem", "fone", "finf"],
+                    help="--manifold spd: the distance -- riem, the affine-invariant distance (the fused kernels); fone / finf, the "
+                         "Finsler distances sum |v_i| / max |v_i| of the vector-valued distance v = log eig(x^-1 y) "
+                         "(Model.forward_vvd + spd_metric, classic loop only: forward, loss and backward through autograd)")
     ap.add_argument("--dims", type=int, default=2)
     ap.add_argument("--scale_init", type=float, default=1.0)
     ap.add_argument("--scale_coef", type=float, default=1.0)
