@@ -405,6 +405,23 @@ int sympa_rsgd_step_clipped(double* table, const double* grad, int64_t num_rows,
                             double weight_decay, double eps, const double* total_sqnorm, double max_norm,
                             int32_t* projected_count, int32_t* status, int32_t* outside_word, void* stream);
 
+/* ---- exponential and logarithm maps, upper and bounded models, dims 1..8 (one row or pair per lane) -----------------
+ * The reference leaves both empty (sympa/manifolds/siegel_manifold.py:156-162) and retracts linearly (siegel_manifold.py:
+ * 74-87: "Simple retraction: x + u. Correct retraction: exp_map(u)").  The maps belong to the invariant metric of the model,
+ * the one the riem distance measures c times the length of (c = 1 upper, c = 2 bounded):
+ *     riem dist(z, expmap(z, u)) = c |u|_z,    logmap(z, expmap(z, u)) = u,    expmap(z1, logmap(z1, z2)) = z2.
+ * z, z1, z2, u, out: [b, 2, n, n]; tangent vectors are complex symmetric, both maps act on sym(u) and on the symmetric part of
+ * the points.  sympa_expmap is pure: no clamp to the eps-interior (u = 0 returns sym(z) bit for bit).  sympa_logmap of two equal
+ * points is an exact 0.  status: SYMPA_ST_NOT_PD (a point outside the domain), SYMPA_ST_NO_CONVERGENCE, SYMPA_ST_NONFINITE.
+ * Other models / dims: SYMPA_ERR_BAD_ARG / SYMPA_ERR_UNSUPPORTED_DIMS.  Formulas and the solve route: siegel_expmap_math.hpp. */
+int sympa_expmap(const double* z, const double* u, int64_t b, int n, int model, double* out, int32_t* status, void* stream);
+int sympa_logmap(const double* z1, const double* z2, int64_t b, int n, int model, double* out, int32_t* status, void* stream);
+/* One RiemannianSGD step over the whole table along the geodesic, in place, ONE launch:
+ *     table <- projx(expmap(table, -lr * egrad2rgrad(table, grad + weight_decay * table)))
+ * projected_count[0] += rows the clamp moved (the exponential map stays inside the domain; projx keeps the eps-interior). */
+int sympa_rsgd_step_exp(double* table, const double* grad, int64_t num_rows, int n, int model, double lr, double weight_decay,
+                        double eps, int32_t* projected_count, int32_t* status, void* stream);
+
 /* The backward half of a training step inside a replayed hipGraph (sympa/runner.py:98-105), dims 1..16 (wave_partials: dims
  * 1..8).  Like
  * sympa_model_loss_backward (grad_table given: fp64-atomic scatter into the dense gradient) or

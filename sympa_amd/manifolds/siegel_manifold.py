@@ -99,11 +99,44 @@ class SiegelManifold(Manifold, ABC):
     def transp(self, x, y, v):  # siegel_manifold.py:142-154: Euclidean transport
         return v
 
-    def expmap(self, x, u):
-        pass
+    # The exponential and logarithm maps (empty in the reference, siegel_manifold.py:156-162).  They belong to the invariant
+    # metric of the model, of which the riem distance measures `dist_scale` times the length:
+    #     riem dist(x, expmap(x, u)) = dist_scale * |u|_x,    logmap(x, expmap(x, u)) = sym(u),    expmap(x, logmap(x, y)) = y.
+    # |u|_x^2 is `inner(x, u, u)` for the upper model; for the bounded model it is Re tr[(I - x conj x)^-1 u (I - conj(x) x)^-1 conj u]
+    # = inner(x, conj u, conj u): the reference's bounded inner (bounded_domain.py:86-116) has the two inverses the other way
+    # round, which agrees at n = 1 and at real points only.
+    # One HIP kernel per call (sympa_expmap / sympa_logmap): float64 [b,2,n,n] on the GPU, dims 1..8.  NOT differentiable in this
+    # version: they run under no_grad and return tensors without a graph.
+    @property
+    def dist_scale(self):
+        """c in riem dist(x, expmap(x, u)) = c * |u|_x: 1 for the upper model, 2 for the bounded one, at any dims."""
+        return {"upper": 1.0, "bounded": 2.0}[self._expmap_model(any_dims=True)]
 
+    def _expmap_model(self, any_dims=False):
+        if self.model_name not in ops.EXPMAP_MODELS:
+            raise NotImplementedError(f"{type(self).__name__} has no exponential / logarithm map: the model has no inner product "
+                                      "to take them from (the reference's inner raises NotImplementedError, compact_dual.py:96)")
+        if not any_dims and not 1 <= self.dims <= ops.EXPMAP_MAX_DIMS:
+            raise NotImplementedError(f"expmap / logmap / geodesic: dims 1..{ops.EXPMAP_MAX_DIMS} (one row per lane), got dims = "
+                                      f"{self.dims}")
+        return self.model_name
+
+    @torch.no_grad()
+    def expmap(self, x, u):
+        """expmap_x(u) of sym(u); pure, no clamp to the eps-interior (follow with projx for that).  Not differentiable."""
+        return ops.expmap(x, u, self._expmap_model())
+
+    @torch.no_grad()
     def logmap(self, x, y):
-        pass
+        """The symmetric tangent vector at x whose geodesic reaches y at time 1; exactly 0 for y = x.  Not differentiable."""
+        return ops.logmap(x, y, self._expmap_model())
+
+    @torch.no_grad()
+    def geodesic(self, t, x, y):
+        """The point at time t of the geodesic from x (t = 0) to y (t = 1): expmap(x, t * logmap(x, y)).  t: a number or a tensor
+        that broadcasts against [b, 1, 1, 1].  Not differentiable."""
+        model = self._expmap_model()
+        return ops.expmap(x, t * ops.logmap(x, y, model), model)
 
     def _check_vector_on_tangent(self, x, u, *, atol=1e-5, rtol=1e-5):
         pass

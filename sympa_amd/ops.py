@@ -996,6 +996,71 @@ def rsgd_step_(table, grad, model, lr, weight_decay=0.0, eps=None, counter=None,
     return table
 
 
+# ---------------------------------------------------------------------------------------------------
+# exponential / logarithm maps and the RiemannianSGD step along the geodesic (C-ABI sympa_expmap / sympa_logmap /
+# sympa_rsgd_step_exp): upper and bounded models, dims 1..8
+# ---------------------------------------------------------------------------------------------------
+EXPMAP_MODELS = ("upper", "bounded")
+EXPMAP_MAX_DIMS = 8
+
+
+def _expmap_args(model, n):
+    if model not in EXPMAP_MODELS:
+        raise NotImplementedError(f"the exponential / logarithm maps exist for the upper and bounded models, not for {model!r} "
+                                  "(the compact dual has no inner product, compact_dual.py:96)")
+    if not 1 <= n <= EXPMAP_MAX_DIMS:
+        raise NotImplementedError(f"the exponential / logarithm maps: dims 1..{EXPMAP_MAX_DIMS}, got {n}")
+
+
+def _expmap_call(entry, a, c, model):
+    lib = _lib.load()
+    a, c = _rows(a.detach(), "the point"), _rows(c.detach(), "the second argument")
+    if a.shape != c.shape or a.device != c.device:
+        raise ValueError(f"both arguments must have one shape on one device, got {tuple(a.shape)} on {a.device} and "
+                         f"{tuple(c.shape)} on {c.device}")
+    _expmap_args(model, a.shape[2])
+    out = torch.empty_like(a)
+    st = _status_buf(a.device)
+    with torch.cuda.device(a.device):
+        rc = getattr(lib, entry)(a.data_ptr(), c.data_ptr(), a.shape[0], a.shape[2], MODEL_IDS[model], out.data_ptr(),
+                                 st.data_ptr(), _stream())
+    _lib.check(rc)
+    return out
+
+
+def expmap(z, u, model):
+    """expmap_z(u) per row (C-ABI sympa_expmap): z, u [b,2,n,n] float64 on the GPU -> [b,2,n,n].  Acts on sym(u); pure (no clamp to
+    the eps-interior).  Not differentiable: the result carries no graph."""
+    return _expmap_call("sympa_expmap", z, u, model)
+
+
+def logmap(z1, z2, model):
+    """logmap_z1(z2) per pair (C-ABI sympa_logmap) -> the symmetric tangent vectors [b,2,n,n]; exactly 0 for equal points.  Not
+    differentiable: the result carries no graph."""
+    return _expmap_call("sympa_logmap", z1, z2, model)
+
+
+def rsgd_step_exp_(table, grad, model, lr, weight_decay=0.0, eps=None, counter=None):
+    """In-place RiemannianSGD step along the geodesic over the whole table, one kernel (C-ABI sympa_rsgd_step_exp):
+    table <- projx(expmap(table, -lr * egrad2rgrad(table, grad + wd table))); `counter` += rows the clamp moved."""
+    lib = _lib.load()
+    _need_gpu(table, "table")
+    if not table.is_contiguous():
+        raise ValueError("table must be contiguous for the in-place step")
+    grad = _rows(grad.detach(), "grad")
+    if table.dtype != torch.float64 or table.shape != grad.shape:
+        raise ValueError(f"table must be a float64 tensor of the gradient's shape {tuple(grad.shape)}, got "
+                         f"{tuple(table.shape)} {table.dtype}")
+    _expmap_args(model, table.shape[2])
+    eps = EPS[torch.float64] if eps is None else float(eps)
+    st = _status_buf(table.device)
+    with torch.cuda.device(table.device):
+        rc = lib.sympa_rsgd_step_exp(table.data_ptr(), grad.data_ptr(), table.shape[0], table.shape[2], MODEL_IDS[model],
+                                     float(lr), float(weight_decay), eps, _opt(counter), st.data_ptr(), _stream())
+    _lib.check(rc)
+    return table
+
+
 RADAM_FUSED_MAX_DIMS = 6
 
 

@@ -18,10 +18,20 @@ from sympa_amd.manifolds.vector import VectorManifold
 class RiemannianSGD(torch.optim.Optimizer):
     graph_capturable = True      # step() keeps no host-side state that changes between calls (sympa_amd.train_step)
 
-    def __init__(self, params, lr, weight_decay=0.0, stabilize=None):
+    def __init__(self, params, lr, weight_decay=0.0, stabilize=None, retraction="linear"):
+        """retraction: "linear" (the reference's retr = projx(x + u), the default) or "exp": the step follows the geodesic,
+        x <- projx(expmap(x, -lr * egrad2rgrad(x, grad + wd x))), one HIP kernel over the table (sympa_rsgd_step_exp).  "exp"
+        exists for device tables of the upper and bounded models with dims <= 8; any other table raises here."""
         if lr < 0.0:
             raise ValueError(f"Invalid learning rate: {lr}")
+        if retraction not in ("linear", "exp"):
+            raise ValueError(f"retraction must be 'linear' or 'exp', got {retraction!r}")
         super().__init__(params, dict(lr=lr, weight_decay=weight_decay))
+        self.retraction = retraction
+        if retraction == "exp":
+            for group in self.param_groups:
+                for p in group["params"]:
+                    self._check_exp_table(p)
         self._stabilize = stabilize   # accepted for signature compatibility; Siegel retr already projects
         # Extension: fold torch.nn.utils.clip_grad_norm_(params, max_norm) (runner.py:115) into the step.  The total
         # norm is accumulated on the device and the factor min(1, max_norm / (norm + 1e-6)) is applied to the
@@ -29,6 +39,23 @@ class RiemannianSGD(torch.optim.Optimizer):
         self.clip_max_norm = None
         self._sqnorm = {}
         self._sqnorm_zeroed_by_caller = False      # GraphedTrainStep zeroes it together with the gradients (one launch)
+
+    @staticmethod
+    def _check_exp_table(p):
+        manifold = getattr(p, "manifold", None)
+        if manifold is None:
+            return          # a parameter on no manifold (the scale): the Euclidean update either way
+        if not isinstance(manifold, SiegelManifold) or manifold.model_name not in ops.EXPMAP_MODELS:
+            raise NotImplementedError(
+                f"retraction='exp' exists for the upper and bounded Siegel models; {type(manifold).__name__} has no exponential "
+                "map here (the compact dual has no inner product, compact_dual.py:96; spd and the vector models step with their "
+                "own retractions): use retraction='linear'")
+        if manifold.dims > ops.EXPMAP_MAX_DIMS:
+            raise NotImplementedError(f"retraction='exp': dims 1..{ops.EXPMAP_MAX_DIMS} (sympa_rsgd_step_exp), got dims = "
+                                      f"{manifold.dims}; use retraction='linear'")
+        if not p.is_cuda or p.dtype != torch.float64:
+            raise NotImplementedError("retraction='exp' is one HIP kernel over a float64 table on the GPU; there is no host "
+                                      f"version (got {p.dtype} on {p.device}): use retraction='linear'")
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -58,7 +85,13 @@ class RiemannianSGD(torch.optim.Optimizer):
                 manifold = getattr(p, "manifold", None)
                 if manifold is not None:
                     ops.table_changed(p)       # the kernels below write through p.data: torch's version counter does not see them
-                if isinstance(manifold, SymmetricPositiveDefinite) and p.is_cuda:
+                if manifold is not None and self.retraction == "exp":
+                    self._check_exp_table(p)       # (a table added or moved after construction)
+                    g = p.grad
+                    if sq is not None:             # the kernel takes no clip factor: scale a copy of the gradient
+                        g = g * (self.clip_max_norm / (sq.sqrt() + 1e-6)).clamp(max=1.0)
+                    ops.rsgd_step_exp_(p.data, g, manifold.model_name, lr, wd, counter=manifold.projected_counter(p.device))
+                elif isinstance(manifold, SymmetricPositiveDefinite) and p.is_cuda:
                     if p.dtype != torch.float64:
                         raise TypeError("the spd table must be float64 (config.py:17-18)")
                     # geoopt's SPD step: retr(x, -lr x sym(g + wd x) x), one kernel over the table

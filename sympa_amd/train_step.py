@@ -68,9 +68,19 @@ def batches_want_source_order(model, batch_size=None, deterministic=False):
     return batch_size is None or int(batch_size) >= floor
 
 
+def _refuse_exp_retraction(optimizer, who):
+    """The fused / sharded step kernels embed the linear retraction projx(x + u) and would silently ignore the option."""
+    if getattr(optimizer, "retraction", "linear") != "linear":
+        raise NotImplementedError(f"{who} steps with the linear retraction inside its fused kernels (sympa_rsgd_step_fused and the "
+                                  f"sharded step embed projx(x + u)); an optimiser built with retraction={optimizer.retraction!r} "
+                                  "runs in the classic loop: Model.fused_loss_backward (or forward + loss + backward), then "
+                                  "optimizer.step()")
+
+
 class GraphedTrainStep:
     def __init__(self, model, optimizer, batch_size, max_grad_norm, device, deterministic=False, accumulate_loss=False,
                  two_kernels=True):
+        _refuse_exp_retraction(optimizer, "GraphedTrainStep")
         # the capture bakes every host-side scalar of the optimiser's step in as an immediate: only optimisers whose step has
         # no host state that changes from step to step may be captured (sympa_amd.optim.RiemannianSGD; RiemannianAdam keeps
         # its powers b^t in device words for this reason).  An optimiser with moments also provides init_state /
@@ -528,6 +538,7 @@ class DistributedTrainStep:
 
     def __init__(self, model, optimizer, batch_size, max_grad_norm, device, mode="dense", group=None, capture_collective=None,
                  accumulate_loss=True, deterministic=None):
+        _refuse_exp_retraction(optimizer, "DistributedTrainStep")
         import torch.distributed as dist
         from sympa_amd.distributed import GradientExchange
         from sympa_amd.optim import RiemannianSGD

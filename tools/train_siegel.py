@@ -119,11 +119,16 @@ def train(args, log=print):
     if finsler is not None and (world > 1 or args.grad_exchange != "none" or hops is not None):
         raise SystemExit(f"--spd-metric {finsler}: the classic single-GPU loop over listed triplets only (no gradient exchange, no "
                          "--sampled-pairs)")
+    retraction = getattr(args, "retraction", "linear")
+    if retraction == "exp" and (args.optim != "rsgd" or world > 1 or args.grad_exchange != "none"):
+        raise SystemExit("--retraction exp: RiemannianSGD in the classic single-GPU loop only (the graphed, fused and distributed "
+                         "steps and RiemannianAdam embed the linear retraction)")
     model = Model(args).to(dev)
     if args.optim == "radam":        # train.py:69-70
         opt = RiemannianAdam(model.parameters(), lr=args.learning_rate * world, eps=1e-7, stabilize=None)
     else:                            # train.py:66-68
-        opt = RiemannianSGD(model.parameters(), lr=args.learning_rate * world, weight_decay=0.0, stabilize=None)
+        opt = RiemannianSGD(model.parameters(), lr=args.learning_rate * world, weight_decay=0.0, stabilize=None,
+                            retraction=retraction)
     radius = upper = None
     eval_hops = hops
     label_max = None
@@ -164,7 +169,7 @@ def train(args, log=print):
     graphed = GraphedTrainStep(model, opt, batch, args.max_grad_norm, dev,
                                deterministic=True if args.deterministic else None, accumulate_loss=True) \
         if (world == 1 and args.graph_step and args.grad_exchange == "none" and args.manifold not in ops.VECTOR_MODEL_IDS
-            and finsler is None) else None
+            and finsler is None and retraction == "linear") else None      # (exp: the classic loop with the eager optimiser)
     # (the vector models train through the classic loop below: fused loss + backward rows + scatter, clip, then the optimiser's
     # step -- RiemannianSGD or, with --optim radam, RiemannianAdam: one kernel over the table either way)
     if args.manifold in ops.VECTOR_MODEL_IDS and (world > 1 or args.grad_exchange != "none"):
@@ -307,6 +312,9 @@ def parser():
     ap.add_argument("--train_scale", action="store_true", default=False)
     ap.add_argument("--learning_rate", type=float, default=1e-2)
     ap.add_argument("--optim", default="rsgd", choices=["rsgd", "radam"])
+    ap.add_argument("--retraction", default="linear", choices=["linear", "exp"],
+                    help="rsgd: linear = the reference's projx(x + u); exp = the step follows the geodesic (sympa_rsgd_step_exp; upper "
+                         "and bounded, dims <= 8), in the classic loop with the eager optimiser")
     ap.add_argument("--max_grad_norm", type=float, default=50.0)
     ap.add_argument("--batch_size", type=int, default=512)
     ap.add_argument("--epochs", type=int, default=50)
