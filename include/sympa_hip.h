@@ -422,6 +422,23 @@ int sympa_logmap(const double* z1, const double* z2, int64_t b, int n, int model
 int sympa_rsgd_step_exp(double* table, const double* grad, int64_t num_rows, int n, int model, double lr, double weight_decay,
                         double eps, int32_t* projected_count, int32_t* status, void* stream);
 
+/* ---- parallel transport along geodesics, upper and bounded models, dims 1..8 (one row per lane) ---------------------
+ * The reference approximates (sympa/manifolds/siegel_manifold.py:142-154: "The formula for the parallel transport is very
+ * complicated so we approximate it with the Euclidean parallel transport").  These are the transport of the invariant metric's
+ * Levi-Civita connection, one congruence v' = G v G^T per row; z, z1, z2, u, v, out_y, out_v: [b, 2, n, n], tangent vectors
+ * complex symmetric (the entries act on sym(u), sym(v) and the symmetric part of the points).
+ * sympa_transp_exp (siegel_manifold.py:142-154): out_v = v transported from z along t -> expmap(z, t u) to expmap(z, u); with
+ * out_y (may be NULL) out_y = expmap(z, u) from the same factor, eigendecomposition and solve.  u = 0 returns sym(v) (and
+ * sym(z)) bit for bit.  out_v may alias v, out_y may alias z.  A tangent so long that tanh rounds to 1 sets status, as in
+ * sympa_expmap.  status: SYMPA_ST_NOT_PD, SYMPA_ST_NO_CONVERGENCE, SYMPA_ST_NONFINITE.  Other models / dims:
+ * SYMPA_ERR_BAD_ARG / SYMPA_ERR_UNSUPPORTED_DIMS.  Formulas and the evaluation form: siegel_transp_math.hpp. */
+int sympa_transp_exp(const double* z, const double* u, const double* v, int64_t b, int n, int model, double* out_y, double* out_v,
+                     int32_t* status, void* stream);
+/* sympa_transp (siegel_manifold.py:142-154): out_v = v transported from z1 to z2 along the geodesic between them; logmap(z1, z2)
+ * is never formed.  z2 = z1 returns sym(v) bit for bit.  out_v may alias v. */
+int sympa_transp(const double* z1, const double* z2, const double* v, int64_t b, int n, int model, double* out_v, int32_t* status,
+                 void* stream);
+
 /* The backward half of a training step inside a replayed hipGraph (sympa/runner.py:98-105), dims 1..16 (wave_partials: dims
  * 1..8).  Like
  * sympa_model_loss_backward (grad_table given: fp64-atomic scatter into the dense gradient) or

@@ -1,0 +1,11 @@
+// gfx950 instantiations of the parallel transport along geodesics, upper model, dims 1..8 (siegel_transp_kernel.hpp).
+#include "siegel_transp_kernel.hpp"
+
+namespace sympa_hip {
+
+int launch_transp_upper(int op, int n, const double* a, const double* c, const double* v, double* out_y, double* out_v, int64_t b,
+                        int32_t* status, hipStream_t s) {
+    return launch_transp_model<sympa::MODEL_UPPER>(op, n, a, c, v, out_y, out_v, b, status, s);
+}
+
+}  // namespace sympa_hip

@@ -97,6 +97,8 @@ class SiegelManifold(Manifold, ABC):
         return self.egrad2rgrad(x, u)
 
     def transp(self, x, y, v):  # siegel_manifold.py:142-154: Euclidean transport
+        # stays the identity (RiemannianAdam is pinned to it); the transport of the invariant metric is parallel_transport /
+        # transp_follow_expmap / expmap_transp below
         return v
 
     # The exponential and logarithm maps (empty in the reference, siegel_manifold.py:156-162).  They belong to the invariant
@@ -137,6 +139,40 @@ class SiegelManifold(Manifold, ABC):
         that broadcasts against [b, 1, 1, 1].  Not differentiable."""
         model = self._expmap_model()
         return ops.expmap(x, t * ops.logmap(x, y, model), model)
+
+    # Parallel transport along geodesics, for the same invariant metric (the reference approximates it by the identity,
+    # siegel_manifold.py:142-154, which `transp` keeps).  geoopt's names; one HIP kernel per call (sympa_transp_exp /
+    # sympa_transp), float64 [b,2,n,n] on the GPU, dims 1..8, under no_grad and NOT differentiable, with the refusals of expmap.
+    # The transport preserves `invariant_inner`.
+    @torch.no_grad()
+    def transp_follow_expmap(self, x, u, v):
+        """sym(v) transported from x along t -> expmap(x, t u) to expmap(x, u); u = 0 returns sym(v) bit for bit."""
+        return ops.transp_exp(x, u, v, self._expmap_model())
+
+    @torch.no_grad()
+    def expmap_transp(self, x, u, v):
+        """(expmap(x, u), the transport of sym(v) to it) from one kernel."""
+        return ops.transp_exp(x, u, v, self._expmap_model(), return_point=True)
+
+    @torch.no_grad()
+    def parallel_transport(self, x, y, v):
+        """sym(v) transported from x to y along the geodesic between them; y = x returns sym(v) bit for bit."""
+        return ops.transp(x, y, v, self._expmap_model())
+
+    def invariant_inner(self, x, u, v=None):
+        """The inner product of the invariant metric, the one the maps and the transport belong to, in the layout of `inner`
+        (host torch, any device): `inner` itself for the upper model; Re tr[(I - x conj x)^-1 u (I - conj(x) x)^-1 conj v] for the
+        bounded model, whose reference `inner` has the two inverses the other way round."""
+        model = self._expmap_model(any_dims=True)
+        if v is None:
+            v = u
+        if model == "upper":
+            return self.inner(x, u, v)
+        xc, uc, vc = (torch.complex(t[:, 0], t[:, 1]) for t in (x, u, v))
+        eye = torch.eye(x.shape[-1], dtype=xc.dtype, device=x.device)
+        res = torch.linalg.inv(eye - xc @ xc.conj()) @ uc @ torch.linalg.inv(eye - xc.conj() @ xc) @ vc.conj()
+        real = res.real.diagonal(dim1=-2, dim2=-1).sum(-1, keepdim=True).unsqueeze(-1)
+        return torch.stack((real, real), dim=1)
 
     def _check_vector_on_tangent(self, x, u, *, atol=1e-5, rtol=1e-5):
         pass

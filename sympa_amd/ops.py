@@ -1061,6 +1061,49 @@ def rsgd_step_exp_(table, grad, model, lr, weight_decay=0.0, eps=None, counter=N
     return table
 
 
+# ---------------------------------------------------------------------------------------------------
+# parallel transport along geodesics (C-ABI sympa_transp_exp / sympa_transp): upper and bounded models, dims 1..8
+# ---------------------------------------------------------------------------------------------------
+def _transp_rows(a, c, v, what):
+    a, c, v = _rows(a.detach(), "the point"), _rows(c.detach(), what), _rows(v.detach(), "the vector")
+    if not (a.shape == c.shape == v.shape and a.device == c.device == v.device):
+        raise ValueError(f"all three arguments must have one shape on one device, got {tuple(a.shape)} on {a.device}, "
+                         f"{tuple(c.shape)} on {c.device} and {tuple(v.shape)} on {v.device}")
+    return a, c, v
+
+
+def transp_exp(x, u, v, model, return_point=False):
+    """v transported from x along t -> expmap(x, t u) to y = expmap(x, u), per row (C-ABI sympa_transp_exp): x, u, v [b,2,n,n]
+    float64 on the GPU -> v' [b,2,n,n], or (y, v') with return_point (one kernel: the factor, the eigendecomposition and the
+    solve are shared).  Acts on sym(u), sym(v); u = 0 returns sym(v) bit for bit.  Not differentiable: no graph."""
+    lib = _lib.load()
+    x, u, v = _transp_rows(x, u, v, "the tangent vector")
+    _expmap_args(model, x.shape[2])
+    out_v = torch.empty_like(x)
+    out_y = torch.empty_like(x) if return_point else None
+    st = _status_buf(x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.sympa_transp_exp(x.data_ptr(), u.data_ptr(), v.data_ptr(), x.shape[0], x.shape[2], MODEL_IDS[model],
+                                  _opt(out_y), out_v.data_ptr(), st.data_ptr(), _stream())
+    _lib.check(rc)
+    return (out_y, out_v) if return_point else out_v
+
+
+def transp(x, y, v, model):
+    """v transported from x to y along the geodesic between them, per row (C-ABI sympa_transp) -> v' [b,2,n,n]; logmap(x, y) is
+    never formed, y = x returns sym(v) bit for bit.  Not differentiable: no graph."""
+    lib = _lib.load()
+    x, y, v = _transp_rows(x, y, v, "the second point")
+    _expmap_args(model, x.shape[2])
+    out_v = torch.empty_like(x)
+    st = _status_buf(x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.sympa_transp(x.data_ptr(), y.data_ptr(), v.data_ptr(), x.shape[0], x.shape[2], MODEL_IDS[model],
+                              out_v.data_ptr(), st.data_ptr(), _stream())
+    _lib.check(rc)
+    return out_v
+
+
 RADAM_FUSED_MAX_DIMS = 6
 
 
