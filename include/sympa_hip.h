@@ -421,6 +421,21 @@ int sympa_logmap(const double* z1, const double* z2, int64_t b, int n, int model
  * projected_count[0] += rows the clamp moved (the exponential map stays inside the domain; projx keeps the eps-interior). */
 int sympa_rsgd_step_exp(double* table, const double* grad, int64_t num_rows, int n, int model, double lr, double weight_decay,
                         double eps, int32_t* projected_count, int32_t* status, void* stream);
+/* One RiemannianAdam step over the whole table along the geodesic, in place, ONE launch, dims 1..8:
+ *     g  = sym(egrad2rgrad(table, coef * grad + weight_decay * table)),   m1 = beta1 sym(exp_avg) + (1 - beta1) g,
+ *     s1 = beta2 exp_avg_sq + (1 - beta2) |g|^2   with the norm of the invariant metric, the one the maps belong to,
+ *     alpha = lr / ((1 - bias_pows[0]) (sqrt(s1 / (1 - bias_pows[1])) + eps_adam)),
+ *     table <- projx(expmap(table, -alpha m1)),  exp_avg <- m1 parallel-transported along that geodesic (sympa_transp_exp with
+ *     out_y: one factor, one eigendecomposition, one solve),  exp_avg_sq <- s1.
+ * exp_avg [num_rows, 2, n, n], exp_avg_sq [num_rows]; bias_pows: device words (beta1^t, beta2^t) of this step, as in
+ * sympa_radam_step.  total_sqnorm (device, may be NULL: no clip): coef = min(1, max_norm / (sqrt(total_sqnorm[0]) + 1e-6)), else
+ * coef = 1.  projected_count[0] += rows the clamp moved; exp_avg of such a row stays as transported.  A zero gradient on zero
+ * moments returns sym(table) bit for bit; so does lr = 0, with exp_avg <- m1.  status as sympa_rsgd_step_exp.  Other models /
+ * dims: SYMPA_ERR_BAD_ARG / SYMPA_ERR_UNSUPPORTED_DIMS, before any launch. */
+int sympa_radam_step_exp(double* table, const double* grad, double* exp_avg, double* exp_avg_sq, int64_t num_rows, int n, int model,
+                         double lr, double beta1, double beta2, double eps_adam, double weight_decay, const double* bias_pows,
+                         double eps, const double* total_sqnorm, double max_norm, int32_t* projected_count, int32_t* status,
+                         void* stream);
 
 /* ---- parallel transport along geodesics, upper and bounded models, dims 1..8 (one row per lane) ---------------------
  * The reference approximates (sympa/manifolds/siegel_manifold.py:142-154: "The formula for the parallel transport is very

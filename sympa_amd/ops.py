@@ -1061,6 +1061,35 @@ def rsgd_step_exp_(table, grad, model, lr, weight_decay=0.0, eps=None, counter=N
     return table
 
 
+def radam_step_exp_(table, grad, exp_avg, exp_avg_sq, bias_pows, model, lr, betas=(0.9, 0.999), eps_adam=1e-8, weight_decay=0.0,
+                    counter=None, clip_sqnorm=None, max_norm=None, eps=None):
+    """In-place RiemannianAdam step along the geodesic over the whole table, one kernel (C-ABI sympa_radam_step_exp, dims 1..8):
+    table <- projx(expmap(table, -alpha m1)), exp_avg <- m1 parallel-transported along that geodesic, exp_avg_sq <- s1 with the
+    invariant norm.  table / grad / exp_avg [N,2,n,n], exp_avg_sq [N], bias_pows = device tensor
+    (beta1^t, beta2^t) of this step; `counter` += rows the clamp moved.  With clip_sqnorm (1-element device tensor holding the
+    squared total gradient norm) and max_norm, the gradient rows are scaled like clip_grad_norm_ does."""
+    lib = _lib.load()
+    _need_gpu(table, "table")
+    grad = _rows(grad.detach(), "grad")
+    for name, t, shape in (("table", table, grad.shape), ("exp_avg", exp_avg, grad.shape), ("exp_avg_sq", exp_avg_sq, grad.shape[:1]),
+                           ("bias_pows", bias_pows, (2,))):
+        if t.dtype != torch.float64 or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != table.device:
+            raise ValueError(f"{name} must be a contiguous float64 tensor of shape {tuple(shape)} on {table.device}, got "
+                             f"{tuple(t.shape)} {t.dtype} on {t.device}")
+    _expmap_args(model, table.shape[2])
+    if (clip_sqnorm is None) != (max_norm is None):
+        raise ValueError("clip_sqnorm and max_norm go together")
+    eps = EPS[torch.float64] if eps is None else float(eps)
+    st = _status_buf(table.device)
+    with torch.cuda.device(table.device):
+        rc = lib.sympa_radam_step_exp(table.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), table.shape[0],
+                                      table.shape[2], MODEL_IDS[model], float(lr), float(betas[0]), float(betas[1]), float(eps_adam),
+                                      float(weight_decay), bias_pows.data_ptr(), eps, _opt(clip_sqnorm),
+                                      0.0 if max_norm is None else float(max_norm), _opt(counter), st.data_ptr(), _stream())
+    _lib.check(rc)
+    return table
+
+
 # ---------------------------------------------------------------------------------------------------
 # parallel transport along geodesics (C-ABI sympa_transp_exp / sympa_transp): upper and bounded models, dims 1..8
 # ---------------------------------------------------------------------------------------------------

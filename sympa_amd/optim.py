@@ -15,6 +15,24 @@ from sympa_amd.manifolds.spd import SymmetricPositiveDefinite
 from sympa_amd.manifolds.vector import VectorManifold
 
 
+def _check_exp_table(p):
+    """retraction="exp" of either optimiser: what the one-kernel geodesic steps (sympa_rsgd_step_exp, sympa_radam_step_exp) take."""
+    manifold = getattr(p, "manifold", None)
+    if manifold is None:
+        return          # a parameter on no manifold (the scale): the Euclidean update either way
+    if not isinstance(manifold, SiegelManifold) or manifold.model_name not in ops.EXPMAP_MODELS:
+        raise NotImplementedError(
+            f"retraction='exp' exists for the upper and bounded Siegel models; {type(manifold).__name__} has no exponential "
+            "map here (the compact dual has no inner product, compact_dual.py:96; spd and the vector models step with their "
+            "own retractions): use retraction='linear'")
+    if manifold.dims > ops.EXPMAP_MAX_DIMS:
+        raise NotImplementedError(f"retraction='exp': dims 1..{ops.EXPMAP_MAX_DIMS} (sympa_rsgd_step_exp, sympa_radam_step_exp), "
+                                  f"got dims = {manifold.dims}; use retraction='linear'")
+    if not p.is_cuda or p.dtype != torch.float64:
+        raise NotImplementedError("retraction='exp' is one HIP kernel over a float64 table on the GPU; there is no host "
+                                  f"version (got {p.dtype} on {p.device}): use retraction='linear'")
+
+
 class RiemannianSGD(torch.optim.Optimizer):
     graph_capturable = True      # step() keeps no host-side state that changes between calls (sympa_amd.train_step)
 
@@ -40,22 +58,7 @@ class RiemannianSGD(torch.optim.Optimizer):
         self._sqnorm = {}
         self._sqnorm_zeroed_by_caller = False      # GraphedTrainStep zeroes it together with the gradients (one launch)
 
-    @staticmethod
-    def _check_exp_table(p):
-        manifold = getattr(p, "manifold", None)
-        if manifold is None:
-            return          # a parameter on no manifold (the scale): the Euclidean update either way
-        if not isinstance(manifold, SiegelManifold) or manifold.model_name not in ops.EXPMAP_MODELS:
-            raise NotImplementedError(
-                f"retraction='exp' exists for the upper and bounded Siegel models; {type(manifold).__name__} has no exponential "
-                "map here (the compact dual has no inner product, compact_dual.py:96; spd and the vector models step with their "
-                "own retractions): use retraction='linear'")
-        if manifold.dims > ops.EXPMAP_MAX_DIMS:
-            raise NotImplementedError(f"retraction='exp': dims 1..{ops.EXPMAP_MAX_DIMS} (sympa_rsgd_step_exp), got dims = "
-                                      f"{manifold.dims}; use retraction='linear'")
-        if not p.is_cuda or p.dtype != torch.float64:
-            raise NotImplementedError("retraction='exp' is one HIP kernel over a float64 table on the GPU; there is no host "
-                                      f"version (got {p.dtype} on {p.device}): use retraction='linear'")
+    _check_exp_table = staticmethod(_check_exp_table)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -142,17 +145,35 @@ class RiemannianAdam(torch.optim.Optimizer):
     section 21): exp_avg_sq is [N], one value per point, and exp_avg is carried to the new point by the affine-invariant parallel
     transport along the step.  Parameters without a manifold get the ordinary Adam update.  amsgrad is not built.
 
+    retraction: "linear" (the default: everything above) or "exp" for device tables of the upper and bounded models with dims <= 8
+    (any other table raises NotImplementedError at construction and in step()).  With "exp" the step follows the geodesic and
+    exp_avg is carried by the parallel transport of the invariant metric, ONE kernel over the table (sympa_radam_step_exp,
+    DESIGN.md section 26):
+        g  <- sym(egrad2rgrad(x, grad + weight_decay * x)),   m1 <- b1 sym(m) + (1 - b1) g
+        v  <- b2 v + (1 - b2) |g|_x^2                         (the INVARIANT norm, manifold.invariant_inner: the one expmap belongs to)
+        u  <- -lr * (m1 / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps)
+        x  <- projx(expmap(x, u)),   m <- m1 transported along t -> expmap(x, t u)
+    so a first step has the invariant length lr |g| / (|g| + eps).  The state has the shapes of the linear step's (exp_avg_sq [N]).
+
     The powers b1^t, b2^t live in two device words per parameter and are advanced by the step itself, so nothing the step
     computes depends on host state that changes from call to call: the step can be captured in a hipGraph
     (sympa_amd.train_step.GraphedTrainStep, classic mode) like RiemannianSGD's.  group["step"] still counts the host-side
     calls, for information only."""
     graph_capturable = True
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, stabilize=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, stabilize=None,
+                 retraction="linear"):
         if amsgrad:
             raise NotImplementedError("amsgrad is not built")
+        if retraction not in ("linear", "exp"):
+            raise ValueError(f"retraction must be 'linear' or 'exp', got {retraction!r}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, step=0))
         self._stabilize = stabilize
+        self.retraction = retraction
+        if retraction == "exp":
+            for group in self.param_groups:
+                for p in group["params"]:
+                    _check_exp_table(p)
         for group in self.param_groups:
             for p in group["params"]:
                 if getattr(getattr(p, "manifold", None), "model_name", None) == "dual":
@@ -228,6 +249,8 @@ class RiemannianAdam(torch.optim.Optimizer):
                 siegel = isinstance(manifold, SiegelManifold) and p.is_cuda
                 if manifold is not None:
                     ops.table_changed(p)       # (see RiemannianSGD.step)
+                    if self.retraction == "exp":
+                        _check_exp_table(p)        # (a table added or moved after construction)
                 if isinstance(manifold, SymmetricPositiveDefinite) and not p.is_cuda:
                     raise NotImplementedError("RiemannianAdam on the spd table is one HIP kernel over the table "
                                               "(sympa_spd_radam_step) and is not built for a table on the host: move the model to "
@@ -239,6 +262,11 @@ class RiemannianAdam(torch.optim.Optimizer):
                 state = self._init_param_state(p, (b1, b2), group["step"] - 1)
                 m, v = state["exp_avg"], state["exp_avg_sq"]
                 pows = state["bias_pows"].mul_(state["betas"])      # (b1^t, b2^t), t = steps this parameter has taken: one launch
+                if manifold is not None and self.retraction == "exp":
+                    # the whole row update in one kernel: moments, the geodesic step, exp_avg transported along it
+                    ops.radam_step_exp_(p.data, p.grad, m, v, state["bias_pows"], manifold.model_name, lr, (b1, b2), eps, wd,
+                                        counter=manifold.projected_counter(p.device))
+                    continue
                 if isinstance(manifold, VectorManifold):
                     if p.dtype != torch.float64:
                         raise TypeError("a vector model's table must be float64 (config.py:17-18)")

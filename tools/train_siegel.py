@@ -120,12 +120,12 @@ def train(args, log=print):
         raise SystemExit(f"--spd-metric {finsler}: the classic single-GPU loop over listed triplets only (no gradient exchange, no "
                          "--sampled-pairs)")
     retraction = getattr(args, "retraction", "linear")
-    if retraction == "exp" and (args.optim != "rsgd" or world > 1 or args.grad_exchange != "none"):
-        raise SystemExit("--retraction exp: RiemannianSGD in the classic single-GPU loop only (the graphed, fused and distributed "
-                         "steps and RiemannianAdam embed the linear retraction)")
+    if retraction == "exp" and (world > 1 or args.grad_exchange != "none"):
+        raise SystemExit("--retraction exp: RiemannianSGD or RiemannianAdam in the classic single-GPU loop only (the graphed, fused "
+                         "and distributed steps embed the linear retraction)")
     model = Model(args).to(dev)
     if args.optim == "radam":        # train.py:69-70
-        opt = RiemannianAdam(model.parameters(), lr=args.learning_rate * world, eps=1e-7, stabilize=None)
+        opt = RiemannianAdam(model.parameters(), lr=args.learning_rate * world, eps=1e-7, stabilize=None, retraction=retraction)
     else:                            # train.py:66-68
         opt = RiemannianSGD(model.parameters(), lr=args.learning_rate * world, weight_decay=0.0, stabilize=None,
                             retraction=retraction)
@@ -313,8 +313,9 @@ def parser():
     ap.add_argument("--learning_rate", type=float, default=1e-2)
     ap.add_argument("--optim", default="rsgd", choices=["rsgd", "radam"])
     ap.add_argument("--retraction", default="linear", choices=["linear", "exp"],
-                    help="rsgd: linear = the reference's projx(x + u); exp = the step follows the geodesic (sympa_rsgd_step_exp; upper "
-                         "and bounded, dims <= 8), in the classic loop with the eager optimiser")
+                    help="linear = the reference's projx(x + u); exp = the step follows the geodesic (rsgd: sympa_rsgd_step_exp; radam: "
+                         "sympa_radam_step_exp, exp_avg parallel-transported; upper and bounded, dims <= 8), in the classic loop with "
+                         "the eager optimiser")
     ap.add_argument("--max_grad_norm", type=float, default=50.0)
     ap.add_argument("--batch_size", type=int, default=512)
     ap.add_argument("--epochs", type=int, default=50)
