@@ -5,6 +5,9 @@
 // Order of row i: self first, then every other column k by the key (d[k], k) -- ascending distance, ties by column index
 // (np.argsort(kind="stable")); -0 counts as +0 and NaN sorts after every number.  With the neighbours nbrs(i) ascending by key
 // as t = 1..deg, r_t = t + #{non-neighbour columns with a smaller key} and AP_i = mean_t(t / r_t) (NaN when deg = 0).
+// A CSR entry equal to its own row is ignored and is no error.  A row with an entry outside [0, num_rows), with more entries
+// than max_degree or with rowptr decreasing across it gets ap = NaN and SYMPA_ST_BAD_INDEX (status[1] counts the bad entries,
+// one for a bad row length): never the AP of the entries that remain.
 //
 // One 256-thread workgroup per row (grid-stride over the block's rows):
 //   (1) the row's neighbour keys (d[c], c) are gathered into LDS and bitonic-sorted there (deg is usually 2..10);
@@ -51,6 +54,7 @@ struct MapArgs {
     double* ap;                      // [rows]
     int32_t* status;
     int fp32;
+    int64_t max_degree;              // the caller's bound on a row's CSR entries (<= the capacity of either kernel)
     int64_t wide_cap;                // entries per workgroup slice of the workspace (wide kernel)
     void* workspace;
 };
@@ -64,10 +68,10 @@ __device__ __forceinline__ void rank_row(const MapArgs& a, const int64_t r, unsi
     const double* row = a.dist + r * a.ld;
     const int64_t beg = a.rowptr[g], end = a.rowptr[g + 1];
     const int64_t raw = end - beg;
-    const int64_t cap = WIDE ? a.wide_cap : MAP_LDS_CAP;
     // the wide kernel's row (block-uniform), unless no wide kernel runs: then the CSR disagrees with max_degree
     if (WIDE ? (raw <= MAP_LDS_CAP) : (raw > MAP_LDS_CAP && a.wide_cap > 0)) return;
-    if (raw < 0 || raw > cap) {                                             // CSR inconsistent with max_degree
+    // max_degree <= MAP_LDS_CAP without a wide kernel, <= wide_cap with one: a row within it fits its arrays
+    if (raw < 0 || raw > a.max_degree) {                                    // CSR inconsistent with max_degree
         if (tid == 0) {
             a.ap[r] = __builtin_nan("");
             if (a.status != nullptr) { atomicOr(&a.status[0], sympa::ST_BAD_INDEX); atomicAdd(&a.status[1], 1); }
@@ -76,9 +80,9 @@ __device__ __forceinline__ void rank_row(const MapArgs& a, const int64_t r, unsi
     }
     int P = 1;
     while (P < raw) P <<= 1;
-    if (tid == 0) s_misc[0] = 0;
+    if (tid == 0) { s_misc[0] = 0; s_misc[1] = 0; }
     __syncthreads();
-    // (1) gather the neighbour keys; self and out-of-range entries become padding (top key), which sorts behind every real key
+    // (1) gather the neighbour keys; self entries become padding (top key), which sorts behind every real key
     int excluded = 0, bad = 0;
     for (int t = tid; t < P; t += MAP_BLOCK) {
         unsigned long long u = ~0ull;
@@ -94,8 +98,16 @@ __device__ __forceinline__ void rank_row(const MapArgs& a, const int64_t r, unsi
         cnt[t] = 0;
     }
     if (excluded) atomicAdd(&s_misc[0], excluded);
-    if (bad && a.status != nullptr) { atomicOr(&a.status[0], sympa::ST_BAD_INDEX); atomicAdd(&a.status[1], bad); }
+    if (bad) {
+        atomicAdd(&s_misc[1], bad);
+        if (a.status != nullptr) { atomicOr(&a.status[0], sympa::ST_BAD_INDEX); atomicAdd(&a.status[1], bad); }
+    }
     __syncthreads();
+    if (s_misc[1] != 0) {                                                  // an out-of-range entry: no AP from the rest of the list
+        if (tid == 0) a.ap[r] = __builtin_nan("");
+        __syncthreads();
+        return;
+    }
     const int deg = (int)raw - s_misc[0];
     // bitonic sort of the P (key, column) pairs, ascending
     for (int k = 2; k <= P; k <<= 1) {
@@ -174,12 +186,12 @@ __global__ __launch_bounds__(MAP_BLOCK) void map_rank_kernel(const MapArgs a) {
     __shared__ unsigned long long keys[MAP_LDS_CAP];
     __shared__ int kcol[MAP_LDS_CAP];
     __shared__ int cnt[MAP_LDS_CAP];
-    __shared__ int misc[1];
+    __shared__ int misc[2];
     for (int64_t r = blockIdx.x; r < a.rows; r += gridDim.x) rank_row<false>(a, r, keys, kcol, cnt, misc);
 }
 
 __global__ __launch_bounds__(MAP_BLOCK) void map_rank_wide_kernel(const MapArgs a) {
-    __shared__ int misc[1];
+    __shared__ int misc[2];
     char* base = reinterpret_cast<char*>(a.workspace) + (int64_t)blockIdx.x * a.wide_cap * 16;
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(base);
     int* kcol = reinterpret_cast<int*>(base + a.wide_cap * 8);
@@ -229,6 +241,7 @@ int sympa_map_rows(const double* dist, int64_t row_count, int64_t ld, int64_t ro
     a.ap = ap;
     a.status = status;
     a.fp32 = (flags & SYMPA_FLAG_FP32_KEYS) ? 1 : 0;
+    a.max_degree = max_degree;
     a.wide_cap = need > 0 ? wide_cap_of(max_degree) : 0;
     a.workspace = workspace;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);

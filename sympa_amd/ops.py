@@ -2162,6 +2162,9 @@ def map_rows(dist_rows, row_begin, neighbors, float32=False, out=None, workspace
     neighbor_csr on the same device; float32=True rounds every distance to fp32 before it is compared (the reference's
     float32 matrix, runner.py:144).  Returns out [R] fp64: ties are broken by column index (a stable sort), so rows with
     exactly tied distances can differ from the reference's unstable np.argsort; NaN for a row without neighbours.
+    A CSR entry equal to its own row is ignored and is no error.  A row with an entry outside [0, N), with more entries than
+    max_degree or with rowptr decreasing across it gets NaN -- never the AP of its remaining entries -- and sets ST_BAD_INDEX
+    in the device status (check_status raises IndexError); the other rows are not affected.
     max_degree (largest CSR row) is read from the device when not given (one host sync)."""
     lib = _lib.load()
     _need_gpu(dist_rows, "dist_rows")
