@@ -643,6 +643,25 @@ int sympa_spd_model_vvd_backward(const double* table, int64_t num_rows, int n, c
                                  const int64_t* dst, int64_t dst_stride, int64_t b, const double* grad_v, double* grad_table,
                                  double* vvd_out, int32_t* status, int flags, void* stream);
 
+/* ---- spd: rows of the all-pairs distance matrix under any of the three metrics --------------------
+ * Runner.build_distance_matrix (sympa/runner.py:142-154) for the spd model, with the pair computed from its number (no pair list):
+ *     out[(i - row_begin) * num_rows + j] = metric(v(x_i, x_j)) * max(scale[0] / scale_coef, 0.1),
+ * i in [row_begin, row_begin + row_count), j in [0, num_rows); table [num_rows, n, n] (upper triangles read), n in [1, 16];
+ * metric = SYMPA_METRIC_RIEM ||v||_2, SYMPA_METRIC_FONE sum_j |v_j|, SYMPA_METRIC_FINF max_j |v_j| of the vector-valued distance
+ * above; scale may be NULL.  The diagonal is exactly 0, also for a point that is not positive definite; every off-diagonal pair
+ * such a point enters comes out NaN and sets SYMPA_ST_NOT_PD; a non-finite value sets SYMPA_ST_NONFINITE.
+ * n = 6..16: sixteen lanes per pair (csrc/spd_allpairs_kernel.hpp: a wave owns one source row and 64 consecutive columns and
+ * factors the source once); n <= 5 or SYMPA_FLAG_GENERIC: one lane per pair.  flags: 0, SYMPA_FLAG_GENERIC and / or
+ * SYMPA_FLAG_NO_SYMMETRY.  For the full matrix (row_begin = 0, row_count = num_rows) without SYMPA_FLAG_NO_SYMMETRY only i <= j
+ * is evaluated and the value is stored at (i, j) and (j, i); a row block always evaluates both orders.
+ * The value at (i, j) depends on x_i, x_j, n, metric, scale and the route (generic or not) alone: a row block is bit for bit the
+ * same rows of the SYMPA_FLAG_NO_SYMMETRY full matrix, whatever the split into blocks, and a NaN pair changes no other pair.
+ * row_count == 0: no-op.  A null table / out, a block outside [0, num_rows], another metric, other flags or scale_coef == 0 with
+ * a scale: SYMPA_ERR_BAD_ARG; n outside [1, 16]: SYMPA_ERR_UNSUPPORTED_DIMS, like the other spd entries; all before any launch. */
+int sympa_spd_all_pairs_dist(const double* table, int64_t num_rows, int n, int64_t row_begin, int64_t row_count,
+                             int metric, const double* scale, double scale_coef, double* out, int32_t* status,
+                             int flags, void* stream);
+
 /* ---- Vector models (manifolds "euclidean", "poincare", "lorentz", "sphere", "prod-hysph", "prod-hyhy", "prod-hyeu",
  * "prod-sphsph": geoopt constructors behind ManifoldFactory, sympa/embeddings.py:130-158, and VectorEmbeddings,
  * sympa/embeddings.py:82-90).  geoopt is not in the reference tree: PARITY UNPINNED like the spd entries; the definitions are

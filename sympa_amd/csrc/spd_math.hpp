@@ -223,6 +223,25 @@ SYMPA_HD double spd_pair_distance(SpdWork& w, const double* __restrict__ px, con
     return out;
 }
 
+// One entry of the all-pairs matrix: spd_pair_distance's eigenvalues a_k (it leaves them in w.d), then the
+// chosen reduction of v_k = log(1 + a_k):  METRIC_RIEM ||v||_2 (spd_pair_distance's own value, bit for bit), METRIC_FONE
+// sum_k |v_k| in index order, METRIC_FINF max_k |v_k|.  Same status bits; a NaN v_k gives NaN under every metric.
+SYMPA_HD double spd_pair_metric(SpdWork& w, const double* __restrict__ px, const double* __restrict__ py, int n, int metric,
+                                int& status) {
+    const double riem = spd_pair_distance(w, px, py, n, status);
+    if (metric == METRIC_RIEM) return riem;
+    double acc = 0.0;
+    bool nan = false;
+    for (int i = 0; i < n; ++i) {
+        const double lg = fabs(d_log1p_signed(w.d[i]));
+        nan = nan || !(lg == lg);
+        acc = (metric == METRIC_FONE) ? acc + lg : fmax(acc, lg);
+    }
+    if (nan) acc = __builtin_nan("");                                            // (fmax drops a NaN operand)
+    if (!(acc == acc) || !(fabs(acc) <= 1.79e308)) status |= ST_NONFINITE;
+    return acc;
+}
+
 // Position of a[k] in the stable ascending order of a[0 .. n): the number of m with (a[m], m) < (a[k], k).  Equal values get
 // distinct ranks; n compares per call, no sort.  (NaN compares false everywhere: the ranks are then not a permutation, which only
 // a pair already flagged ST_NONFINITE / ST_NOT_PD can meet.)

@@ -17,6 +17,11 @@ from sympa_amd.manifolds.spd import spd_metric
 
 # forward() under no_grad takes the packed path (two launches) from this many pairs per call on
 PACKED_MIN_PAIRS = 4096
+# distance_matrix / mean_average_precision / evaluate_all_pairs of the riem spd model keep the [R N, 2] pair list and the gathered
+# pair kernel at these n: sympa_spd_all_pairs_dist measured more than 10 % slower there (n = 16: 1.16-1.19 x the packed pair kernel
+# plus the list, 1.08-1.11 x the dense one; every n <= 15 is within 9 %, n <= 8 faster).  The Finsler metrics have
+# no other route and run the new entry at every n.
+SPD_ALL_PAIRS_PAIR_LIST_DIMS = frozenset({16})
 
 
 class _SpdBatches:
@@ -411,26 +416,46 @@ class Model(nn.Module):
                                      self.scale.data, gs, self.scale_coef, loss_scale)
         return loss
 
-    def distance_matrix(self, row_begin=0, row_count=None):
+    def _spd_all_pairs_metric(self, what):
+        """The metric of the spd all-pairs kernel for this model: manifold.finsler ("fone" / "finf") or "riem".  A Finsler model
+        whose table is on the host has no route at all (its distance is HIP kernels over the table) and says so, before the caller
+        looks at its arguments."""
+        kind = self._spd_finsler()
+        if kind is not None and not self.embeddings.embeds.is_cuda:
+            raise NotImplementedError(f"{what}: the spd model with spd_metric='{kind}' is evaluated by HIP kernels over the table "
+                                      f"and is not built for a table on the host: move the model to the GPU")
+        return kind or "riem"
+
+    def _spd_pair_list_route(self, kind):
+        """riem at the n of SPD_ALL_PAIRS_PAIR_LIST_DIMS keeps the pair-list route (measured faster there)."""
+        return kind == "riem" and int(self.embeddings.embeds.shape[-1]) in SPD_ALL_PAIRS_PAIR_LIST_DIMS
+
+    def distance_matrix(self, row_begin=0, row_count=None, symmetric=False):
         """Extension: the N x N matrix Runner.build_distance_matrix (runner.py:142-154) assembles with N
-        forward calls, as one launch (or one launch per row block).  Diagonal exactly 0."""
-        self._refuse_finsler("distance_matrix")
+        forward calls, as one launch (or one launch per row block).  Diagonal exactly 0.  spd: under the model's own metric
+        (riem, or spd_metric fone / finf), both orders of every pair evaluated, so a row block is bit for bit the same rows of the
+        full matrix; symmetric=True lets the full matrix evaluate i <= j only and store each value twice.  (riem at n = 16 keeps the
+        [R N, 2] pair list and the gathered pair kernel: there a block agrees with the full matrix to rounding only.)"""
         from sympa_amd import ops
         man = self.manifold
         if _is_vector(man):
             # the pair kernel with (i, j) computed from the pair number: no pair list; diagonal exactly 0, exactly symmetric
             return ops.vector_all_pairs_dist(self.embeddings.embeds, man.model_name, self.scale, self.scale_coef, row_begin, row_count)
         if man.model_name == "spd":
-            # the same pairs (i, j) the reference's loop feeds to forward(), through the spd kernel
-            emb = self.embeddings.embeds
-            n_pts = emb.shape[0]
-            row_count = n_pts - row_begin if row_count is None else row_count
-            rows = torch.arange(row_begin, row_begin + row_count, device=emb.device)
-            cols = torch.arange(n_pts, device=emb.device)
-            pairs = torch.stack((rows.repeat_interleave(n_pts), cols.repeat(row_count)), 1)
-            out = ops.spd_model_forward(emb, pairs, self.scale, self.scale_coef).reshape(row_count, n_pts)
-            out[torch.arange(row_count, device=emb.device), rows] = 0.0      # runner.py:152
-            return out
+            # the same pairs (i, j) the reference's loop feeds to forward(), computed from their number (sympa_spd_all_pairs_dist)
+            kind = self._spd_all_pairs_metric("distance_matrix")
+            if self._spd_pair_list_route(kind):
+                emb = self.embeddings.embeds
+                n_pts = emb.shape[0]
+                row_count = n_pts - row_begin if row_count is None else row_count
+                rows = torch.arange(row_begin, row_begin + row_count, device=emb.device)
+                cols = torch.arange(n_pts, device=emb.device)
+                pairs = torch.stack((rows.repeat_interleave(n_pts), cols.repeat(row_count)), 1)
+                out = ops.spd_model_forward(emb, pairs, self.scale, self.scale_coef).reshape(row_count, n_pts)
+                out[torch.arange(row_count, device=emb.device), rows] = 0.0      # runner.py:152
+                return out
+            return ops.spd_all_pairs_dist(self.embeddings.embeds, kind, self.scale, self.scale_coef, row_begin, row_count,
+                                          flags=0 if symmetric else ops.FLAG_NO_SYMMETRY)
         weights = man.metric.weights if man.metric.kind is MetricType.WEIGHTED_SUM else None
         return ops.all_pairs_dist(self.embeddings.embeds, man.model_name, man.metric.kind.value, weights, self.scale,
                                   self.scale_coef, row_begin, row_count)
@@ -439,15 +464,15 @@ class Model(nn.Module):
                                return_rows=False):
         """Extension: Runner.calculate_mAP (runner.py:137-140) on the device, never holding more than a bounded slab of the matrix.
         Rows are produced a block at a time into ONE reused [R, N] buffer (R from max_block_bytes) by the row-oriented all-pairs
-        kernels (packed kernel for upper / bounded dims <= 8, pairwise kernels for dims 9..16; spd: distance_matrix(row_begin,
-        row_count), whose [R * N, 2] pair list is counted against the budget) and each block is ranked by ops.map_rows.
+        kernels (packed kernel for upper / bounded dims <= 8, pairwise kernels for dims 9..16; spd: ops.spd_all_pairs_dist under the
+        model's metric, riem or spd_metric fone / finf) and each block is ranked by ops.map_rows.
         `triples_or_metric`: a sympa_amd.metrics.MeanAveragePrecisionMetric, or what its constructor takes.  dtype=torch.float32
         compares fp32-rounded distances, like the reference's float32 matrix (runner.py:144); torch.float64 the fp64 values.
         With `group` set or a default process group initialised, every rank ranks its own contiguous share of the rows and the
         [N] AP vector is assembled by an exact all-reduce of zero-padded vectors, so the result does not depend on the world size
         or on the block size.  Reads the table only: forward caches and the packed-table state are untouched.  One host sync
         (the returned float); with return_rows=True returns (mAP, AP [N] fp64 device tensor)."""
-        self._refuse_finsler("mean_average_precision")
+        spd_kind = self._spd_all_pairs_metric("mean_average_precision") if self.manifold.model_name == "spd" else None
         from sympa_amd import distributed as sd
         from sympa_amd import metrics as sm
         if dtype not in (torch.float32, torch.float64):
@@ -462,15 +487,18 @@ class Model(nn.Module):
         nbrs = metric.csr(N, dev)
         vec = _is_vector(man)
         spd = man.model_name == "spd"
-        row_bytes = (8 + 16 + 16) * N if spd else 8 * N       # spd: output + [N, 2] pair list + the arange repeats behind it
+        spd_list = spd and self._spd_pair_list_route(spd_kind)
+        row_bytes = (8 + 16 + 16) * N if spd_list else 8 * N       # pair-list route: output + [N, 2] pair list + the arange repeats
         R = max(1, int(max_block_bytes) // row_bytes)
         begin, count = (0, N) if group is None and not sd.dist.is_initialized() else sd.row_shard(N, group)
         R = min(R, max(count, 1))
         ap = torch.zeros(N, dtype=torch.float64, device=dev)
         float32 = dtype == torch.float32
-        if vec:
+        if spd_list:
+            buf = None
+        elif vec or spd:
             buf = torch.empty(R, N, dtype=torch.float64, device=dev) if count > 0 else None
-        elif not spd:
+        else:
             weights = man.metric.weights if man.metric.kind is MetricType.WEIGHTED_SUM else None
             n = table.shape[-1]
             need = ops._lib.load().sympa_all_pairs_workspace_bytes(N, n, ops.MODEL_IDS[man.model_name])
@@ -481,8 +509,11 @@ class Model(nn.Module):
                 r = min(R, begin + count - b)
                 if vec:
                     rows = ops.vector_all_pairs_dist(table, man.model_name, self.scale.detach(), self.scale_coef, b, r, out=buf[:r])
-                elif spd:
+                elif spd_list:
                     rows = self.distance_matrix(b, r)
+                elif spd:
+                    rows = ops.spd_all_pairs_dist(table, spd_kind, self.scale.detach(), self.scale_coef, b, r, out=buf[:r],
+                                                  flags=ops.FLAG_NO_SYMMETRY)
                 else:
                     rows = ops.all_pairs_dist(table, man.model_name, man.metric.kind.value, weights, self.scale.detach(),
                                               self.scale_coef, b, r, out=buf[:r], packed=need > 0, workspace=ws,
@@ -506,7 +537,7 @@ class Model(nn.Module):
         With `group` set or a default process group initialised every rank takes its contiguous
         share of the rows and the zero-padded [N] vectors are combined by an exact all-reduce: bitwise the single-process value.
         One host sync (the returned float)."""
-        self._refuse_finsler("evaluate_all_pairs")
+        spd_kind = self._spd_all_pairs_metric("evaluate_all_pairs") if self.manifold.model_name == "spd" else None
         from sympa_amd import distributed as sd
         from sympa_amd.graph import WeightedGraphDistances
         man = self.manifold
@@ -524,8 +555,8 @@ class Model(nn.Module):
         # a WeightedGraphDistances differs in the dtype of the graph rows and in the kernel that reduces them; the rest is shared
         weighted = isinstance(gd, WeightedGraphDistances)
         reduce_rows = ops.graph_weighted_distortion_rows if weighted else ops.graph_distortion_rows
-        # spd: + the [N, 2] pair list and the arange repeats behind it
-        row_bytes = ((8 if weighted else 4) + 8 + (32 if spd else 0)) * N
+        spd_list = spd and self._spd_pair_list_route(spd_kind)
+        row_bytes = ((8 if weighted else 4) + 8 + (32 if spd_list else 0)) * N      # pair-list route: + the list and its repeats
         R = max(64, (int(max_block_bytes) // row_bytes) // 64 * 64)
         begin, count = (0, N) if group is None and not sd.dist.is_initialized() else sd.row_shard(N, group)
         R = min(R, max(count, 1))
@@ -533,7 +564,7 @@ class Model(nn.Module):
         pairs = torch.zeros(N, dtype=torch.int64, device=dev)
         if count > 0:
             hbuf = torch.empty(R, N, dtype=torch.float64 if weighted else torch.int32, device=dev)
-            if vec:
+            if vec or (spd and not spd_list):
                 dbuf = torch.empty(R, N, dtype=torch.float64, device=dev)
             elif not spd:
                 weights = man.metric.weights if man.metric.kind is MetricType.WEIGHTED_SUM else None
@@ -545,8 +576,11 @@ class Model(nn.Module):
                 r = min(R, begin + count - b)
                 if vec:
                     rows = ops.vector_all_pairs_dist(table, man.model_name, self.scale.detach(), self.scale_coef, b, r, out=dbuf[:r])
-                elif spd:
+                elif spd_list:
                     rows = self.distance_matrix(b, r)
+                elif spd:
+                    rows = ops.spd_all_pairs_dist(table, spd_kind, self.scale.detach(), self.scale_coef, b, r, out=dbuf[:r],
+                                                  flags=ops.FLAG_NO_SYMMETRY)
                 else:
                     rows = ops.all_pairs_dist(table, man.model_name, man.metric.kind.value, weights, self.scale.detach(),
                                               self.scale_coef, b, r, out=dbuf[:r], packed=need > 0, workspace=ws,

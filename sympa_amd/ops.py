@@ -1538,6 +1538,48 @@ def spd_model_vvd_forward(table, triplets, flags=0):
     return vvd
 
 
+SPD_ALL_PAIRS_METRICS = ("riem", "fone", "finf")
+
+
+def spd_all_pairs_dist(table, metric="riem", scale=None, scale_coef=1.0, row_begin=0, row_count=None, out=None, flags=0):
+    """Rows [row_begin, row_begin + row_count) of the spd model's N x N distance matrix under `metric` ("riem", "fone", "finf") times
+    max(scale / scale_coef, 0.1), [row_count, N] fp64 (C-ABI sympa_spd_all_pairs_dist): no pair list, the
+    diagonal exactly 0, every value a function of its own pair alone -- a row block is bit for bit the same rows of the
+    FLAG_NO_SYMMETRY full matrix.  The full matrix without FLAG_NO_SYMMETRY evaluates i <= j only and stores each value twice.
+    flags: 0, FLAG_GENERIC and / or FLAG_NO_SYMMETRY.  `out`: a contiguous float64 [row_count, N] tensor (a slice of rows of a larger
+    buffer is one) that is written and returned."""
+    lib = _lib.load()
+    _need_gpu(table, "table")
+    if table.dtype != torch.float64 or table.dim() != 3 or table.shape[1] != table.shape[2]:
+        raise ValueError(f"spd table must be float64 [N,n,n], got {tuple(table.shape)}")
+    if metric not in SPD_ALL_PAIRS_METRICS:
+        raise ValueError(f"spd all-pairs metric must be one of {SPD_ALL_PAIRS_METRICS}, got {metric!r}")
+    tab = table.detach()
+    tab = tab if tab.is_contiguous() else tab.contiguous()
+    N, n = tab.shape[0], tab.shape[1]
+    row_begin = int(row_begin)
+    row_count = N - row_begin if row_count is None else int(row_count)
+    if row_begin < 0 or row_count < 0 or row_begin + row_count > N:
+        raise ValueError(f"rows [{row_begin}, {row_begin + row_count}) are outside the table's {N}")
+    if out is None:
+        out = torch.empty(row_count, N, dtype=torch.float64, device=tab.device)
+    elif out.dtype != torch.float64 or out.shape != (row_count, N) or not out.is_contiguous() or out.device != tab.device:
+        raise ValueError(f"out must be a contiguous float64 [{row_count}, {N}] tensor on {tab.device}")
+    if row_count == 0 or N == 0:
+        return out
+    sc = None
+    if scale is not None:
+        sc = scale.detach().reshape(-1)[:1].to(device=tab.device, dtype=torch.float64).contiguous()
+    st = _status_buf(tab.device)
+    with torch.cuda.device(tab.device):
+        rc = lib.sympa_spd_all_pairs_dist(_ptr(tab), N, n, row_begin, row_count, METRIC_IDS[metric], _opt(sc), float(scale_coef),
+                                          _ptr(out), _ptr(st), int(flags), _stream())
+    _lib.check(rc)
+    if _debug:
+        check_status(tab.device)
+    return out
+
+
 def spd_vvd_backward(x, y, grad_v, return_vvd=False, flags=0):
     """Backward of the vector-valued distance for pre-gathered points (C-ABI sympa_spd_vvd_bwd): grad_v [b, n] on the ascending v
     -> (grad_x, grad_y) [b, n, n] (and v [b, n] from the backward's own eigen-decomposition with return_vvd)."""
