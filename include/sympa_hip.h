@@ -122,7 +122,8 @@ int sympa_max_dims(void);
 #define SYMPA_FAMILY_SIEGEL_TABLE 2 /* sympa_egrad2rgrad / sympa_projx / sympa_rsgd_step* / sympa_tangent_sqnorm, n = 7..16 */
 #define SYMPA_FAMILY_SPD_FWD 3      /* sympa_spd_dist_fwd / sympa_spd_model_forward, n = 6..16 */
 #define SYMPA_FAMILY_SPD_BWD 4      /* sympa_spd_backward_rows / sympa_spd_loss_backward, n = 3..16 */
-#define SYMPA_FAMILY_SPD_TABLE 5    /* sympa_spd_egrad2rgrad / sympa_spd_rsgd_step / sympa_spd_radam_step, n = 3..16 */
+#define SYMPA_FAMILY_SPD_TABLE 5    /* sympa_spd_egrad2rgrad / sympa_spd_rsgd_step / sympa_spd_radam_step /
+                                       sympa_spd_expmap / _logmap / _geodesic / sympa_spd_rsgd_step_exp, n = 3..16 */
 #define SYMPA_NUM_FAMILIES 6
 int sympa_set_instance_fallback(int family, int model, int n, int on);
 int sympa_get_instance_fallback(int family, int model, int n);
@@ -608,6 +609,29 @@ int sympa_spd_rsgd_step(double* table, const double* grad, int64_t num_rows, int
 int sympa_spd_radam_step(double* table, const double* grad, double* exp_avg, double* exp_avg_sq, int64_t num_rows, int n,
                          double lr, double beta1, double beta2, double eps_adam, double weight_decay, const double* bias_pows,
                          const double* total_sqnorm, double max_norm, int32_t* status, void* stream);
+/* The exponential map, logarithm and geodesic of the affine-invariant metric, and the RiemannianSGD step that moves along the
+ * geodesic (parity unpinned with respect to geoopt like every spd entry).  With x = L L^T and, for a
+ * symmetric W, A = L^-1 W L^-T = V diag(a) V^T:
+ *     expmap(x, u)      = x + L V diag(expm1(a)) V^T L^T,            W = sym(u)     (= x^1/2 exp(x^-1/2 sym(u) x^-1/2) x^1/2)
+ *     logmap(x, y)      =     L V diag(log1p(a)) V^T L^T,            W = y - x
+ *     geodesic(t, x, y) = x + L V diag(expm1(t log1p(a))) V^T L^T,   W = y - x,  any finite t (0: x, 1: y to rounding)
+ *     step:  x <- expmap(x, -lr x S x) = x + L V diag(expm1(-lr c)) V^T L^T,   L^T S L = V diag(c) V^T,
+ *            S = coef sym(grad) + weight_decay x,  coef the folded clip of sympa_spd_rsgd_step (total_sqnorm, max_norm)
+ * x, y, u, out: [b, n, n], fp64; x and y are read as their upper triangles, u as sym(u); the step reads sym(table row), sym(grad
+ * row) and works in place (all of a row's loads stand before its stores).  out may alias nothing.  Outputs are symmetric bit for
+ * bit; u = 0, t = 0, lr = 0 return the (symmetric) point bit for bit and y == x an exact zero logarithm.  The step's result is
+ * positive definite for every step length: no projection, no counter.  n in [1, 16]; flags: 0 or SYMPA_FLAG_GENERIC (the
+ * one-row-per-lane kernel at every n; the default runs sixteen lanes per row for n >= 3).  b == 0: no-op.
+ * SYMPA_ERR_BAD_ARG: null required pointers, b < 0, other flags, a non-finite t, total_sqnorm with max_norm <= 0;
+ * SYMPA_ERR_UNSUPPORTED_DIMS: n outside the range.  An x that does not factor (for logmap / geodesic also a y that is not
+ * positive definite against x) raises SYMPA_ST_NOT_PD, is counted in status[1] as in sympa_spd_rsgd_step, and its output row is
+ * NaN; SYMPA_ST_NONFINITE: a tangent so long that expm1 overflows. */
+int sympa_spd_expmap(const double* x, const double* u, int64_t b, int n, double* out, int32_t* status, int flags, void* stream);
+int sympa_spd_logmap(const double* x, const double* y, int64_t b, int n, double* out, int32_t* status, int flags, void* stream);
+int sympa_spd_geodesic(const double* x, const double* y, double t, int64_t b, int n, double* out, int32_t* status, int flags,
+                       void* stream);
+int sympa_spd_rsgd_step_exp(double* table, const double* grad, int64_t num_rows, int n, double lr, double weight_decay,
+                            const double* total_sqnorm, double max_norm, int32_t* status, int flags, void* stream);
 
 /* ---- spd: the differentiable vector-valued distance ------------------------------------------
  * v [b, n] = log(lam_j) ASCENDING, lam = the eigenvalues of x^-1 y, evaluated as log(1 + a_j), a = the eigenvalues of

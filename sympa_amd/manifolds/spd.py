@@ -87,6 +87,21 @@ class SymmetricPositiveDefinite(Manifold):
         torch here (init / tests); the optimiser uses the fused sympa_spd_rsgd_step."""
         return _sym(x + u + 0.5 * u @ torch.linalg.inv(x) @ u)
 
+    def expmap(self, x, u):
+        """The affine-invariant exponential map x^1/2 exp(x^-1/2 sym(u) x^-1/2) x^1/2 (geoopt SymmetricPositiveDefinite.expmap, AIM):
+        HIP kernels over [b, n, n] float64 device tensors (ops.spd_expmap); not differentiable, no host
+        version.  retr stays geoopt's second-order retraction."""
+        return ops.spd_expmap(x, u)
+
+    def logmap(self, x, y):
+        """x^1/2 log(x^-1/2 y x^-1/2) x^1/2: the tangent at x with expmap(x, .) = y (ops.spd_logmap)."""
+        return ops.spd_logmap(x, y)
+
+    def geodesic(self, t, x, y):
+        """The point of the geodesic from x (t = 0) to y (t = 1) at the real parameter t, one value for all pairs
+        (ops.spd_geodesic)."""
+        return ops.spd_geodesic(x, y, t)
+
     def inner(self, x, u, v=None, keepdim=False):
         """geoopt (AIM): tr(x^-1 u x^-1 v), one number per point; plain torch on any device."""
         xu = torch.linalg.solve(x, u)

@@ -1922,6 +1922,82 @@ def spd_radam_step_(table, grad, exp_avg, exp_avg_sq, bias_pows, lr, betas=(0.9,
     return table
 
 
+SPD_MAX_DIMS = 16       # sympa::SPD_MAX_N
+
+
+def _spd_map(entry, x, second, name, flags, t=None):
+    """the three maps share their checks: float64 [b, n, n] device tensors of one shape and device"""
+    if not (x.is_cuda and second.is_cuda):
+        raise NotImplementedError(f"spd_{entry}: HIP kernels over device tensors (sympa_spd_{entry}); there is no host version "
+                                  f"(x on {x.device}, {name} on {second.device})")
+    lib = _lib.load()
+    x, second = _spd_rows(x.detach(), "x"), _spd_rows(second.detach(), name)
+    if x.shape != second.shape or x.device != second.device:
+        raise ValueError(f"x and {name} must have one shape and device, got {tuple(x.shape)} on {x.device} and "
+                         f"{tuple(second.shape)} on {second.device}")
+    if not 1 <= x.shape[1] <= SPD_MAX_DIMS:
+        raise ValueError(f"spd_{entry}: n in 1..{SPD_MAX_DIMS}, got {x.shape[1]}")
+    if not flags & FLAG_GENERIC:
+        _gate(_sc.SPD_TABLE, "spd", x.shape[1], x.device)
+    out = torch.empty_like(x)
+    st = _status_buf(x.device)
+    with torch.cuda.device(x.device):
+        if t is None:
+            rc = getattr(lib, "sympa_spd_" + entry)(x.data_ptr(), second.data_ptr(), x.shape[0], x.shape[1], out.data_ptr(), st.data_ptr(),
+                                                    int(flags), _stream())
+        else:
+            rc = lib.sympa_spd_geodesic(x.data_ptr(), second.data_ptr(), float(t), x.shape[0], x.shape[1], out.data_ptr(), st.data_ptr(),
+                                        int(flags), _stream())
+    _lib.check(rc)
+    return out
+
+
+def spd_expmap(x, u, flags=0):
+    """The affine-invariant exponential map x^1/2 exp(x^-1/2 sym(u) x^-1/2) x^1/2 of [b, n, n] float64 device tensors (C-ABI
+    sympa_spd_expmap); not differentiable.  flags: 0 or FLAG_GENERIC (one row per lane at every n)."""
+    return _spd_map("expmap", x, u, "u", flags)
+
+
+def spd_logmap(x, y, flags=0):
+    """The logarithm x^1/2 log(x^-1/2 y x^-1/2) x^1/2: the tangent at x whose exponential is y (C-ABI sympa_spd_logmap)."""
+    return _spd_map("logmap", x, y, "y", flags)
+
+
+def spd_geodesic(x, y, t, flags=0):
+    """The point x^1/2 (x^-1/2 y x^-1/2)^t x^1/2 of the geodesic from x (t = 0) to y (t = 1), any finite t (C-ABI
+    sympa_spd_geodesic)."""
+    t = float(t)
+    if t != t or t in (float("inf"), float("-inf")):
+        raise ValueError(f"spd_geodesic: t must be finite, got {t}")
+    return _spd_map("geodesic", x, y, "y", flags, t=t)
+
+
+def spd_rsgd_step_exp_(table, grad, lr, weight_decay=0.0, clip_sqnorm=None, max_norm=None, flags=0):
+    """In-place RiemannianSGD step of an spd table along the geodesic, x <- expmap(x, -lr x sym(coef g + wd x) x), as one kernel
+    (C-ABI sympa_spd_rsgd_step_exp): positive definite for every step length, no projection."""
+    if not (table.is_cuda and grad.is_cuda):
+        raise NotImplementedError("spd_rsgd_step_exp_: one HIP kernel over a device table (sympa_spd_rsgd_step_exp); there is no host "
+                                  f"version (table on {table.device}, grad on {grad.device})")
+    lib = _lib.load()
+    if not table.is_contiguous():
+        raise ValueError("table must be contiguous for the in-place step")
+    grad = _spd_rows(grad.detach(), "grad")
+    if table.dtype != torch.float64 or table.dim() != 3 or table.shape != grad.shape or table.device != grad.device:
+        raise ValueError(f"table must be a float64 [N, n, n] tensor of the gradient's shape {tuple(grad.shape)} on {grad.device}, got "
+                         f"{tuple(table.shape)} {table.dtype} on {table.device}")
+    if not 1 <= table.shape[1] <= SPD_MAX_DIMS:
+        raise ValueError(f"spd_rsgd_step_exp_: n in 1..{SPD_MAX_DIMS}, got {table.shape[1]}")
+    if not flags & FLAG_GENERIC:
+        _gate(_sc.SPD_TABLE, "spd", table.shape[1], table.device)
+    st = _status_buf(table.device)
+    with torch.cuda.device(table.device):
+        rc = lib.sympa_spd_rsgd_step_exp(table.data_ptr(), grad.data_ptr(), table.shape[0], table.shape[1], float(lr),
+                                         float(weight_decay), _opt(clip_sqnorm), float(max_norm) if max_norm is not None else 0.0,
+                                         st.data_ptr(), int(flags), _stream())
+    _lib.check(rc)
+    return table
+
+
 # ---------------------------------------------------------------------------------------------------
 # Vector models (C-ABI sympa_vector_*; DESIGN.md section 19): points are rows of `dims` doubles
 # ---------------------------------------------------------------------------------------------------

@@ -15,11 +15,19 @@ from sympa_amd.manifolds.spd import SymmetricPositiveDefinite
 from sympa_amd.manifolds.vector import VectorManifold
 
 
-def _check_exp_table(p):
-    """retraction="exp" of either optimiser: what the one-kernel geodesic steps (sympa_rsgd_step_exp, sympa_radam_step_exp) take."""
+def _check_exp_table(p, spd=False):
+    """retraction="exp" of either optimiser: what the one-kernel geodesic steps (sympa_rsgd_step_exp, sympa_radam_step_exp) take.
+    spd=True (RiemannianSGD): a device float64 spd table as well (sympa_spd_rsgd_step_exp; there is no geodesic RiemannianAdam
+    for spd)."""
     manifold = getattr(p, "manifold", None)
     if manifold is None:
         return          # a parameter on no manifold (the scale): the Euclidean update either way
+    if spd and isinstance(manifold, SymmetricPositiveDefinite):
+        if not p.is_cuda or p.dtype != torch.float64:
+            raise NotImplementedError("retraction='exp' on the spd table is one HIP kernel over a float64 table on the GPU "
+                                      f"(sympa_spd_rsgd_step_exp); there is no host version (got {p.dtype} on {p.device}): use "
+                                      "retraction='linear'")
+        return
     if not isinstance(manifold, SiegelManifold) or manifold.model_name not in ops.EXPMAP_MODELS:
         raise NotImplementedError(
             f"retraction='exp' exists for the upper and bounded Siegel models; {type(manifold).__name__} has no exponential "
@@ -39,7 +47,8 @@ class RiemannianSGD(torch.optim.Optimizer):
     def __init__(self, params, lr, weight_decay=0.0, stabilize=None, retraction="linear"):
         """retraction: "linear" (the reference's retr = projx(x + u), the default) or "exp": the step follows the geodesic,
         x <- projx(expmap(x, -lr * egrad2rgrad(x, grad + wd x))), one HIP kernel over the table (sympa_rsgd_step_exp).  "exp"
-        exists for device tables of the upper and bounded models with dims <= 8; any other table raises here."""
+        exists for device tables of the upper and bounded models with dims <= 8 and for device float64 spd tables
+        (sympa_spd_rsgd_step_exp: the affine-invariant geodesic, no projection); any other table raises here."""
         if lr < 0.0:
             raise ValueError(f"Invalid learning rate: {lr}")
         if retraction not in ("linear", "exp"):
@@ -49,7 +58,7 @@ class RiemannianSGD(torch.optim.Optimizer):
         if retraction == "exp":
             for group in self.param_groups:
                 for p in group["params"]:
-                    self._check_exp_table(p)
+                    self._check_exp_table(p, spd=True)
         self._stabilize = stabilize   # accepted for signature compatibility; Siegel retr already projects
         # Extension: fold torch.nn.utils.clip_grad_norm_(params, max_norm) (runner.py:115) into the step.  The total
         # norm is accumulated on the device and the factor min(1, max_norm / (norm + 1e-6)) is applied to the
@@ -89,7 +98,11 @@ class RiemannianSGD(torch.optim.Optimizer):
                 if manifold is not None:
                     ops.table_changed(p)       # the kernels below write through p.data: torch's version counter does not see them
                 if manifold is not None and self.retraction == "exp":
-                    self._check_exp_table(p)       # (a table added or moved after construction)
+                    self._check_exp_table(p, spd=True)       # (a table added or moved after construction)
+                    if isinstance(manifold, SymmetricPositiveDefinite):
+                        ops.spd_rsgd_step_exp_(p.data, p.grad, lr, wd, clip_sqnorm=sq,
+                                               max_norm=self.clip_max_norm if sq is not None else None)
+                        continue
                     g = p.grad
                     if sq is not None:             # the kernel takes no clip factor: scale a copy of the gradient
                         g = g * (self.clip_max_norm / (sq.sqrt() + 1e-6)).clamp(max=1.0)

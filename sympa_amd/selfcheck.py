@@ -192,7 +192,11 @@ def _check_spd_table(model, n, dev):
         ops.spd_rsgd_step_(t, grad, 1e-2)
         ta, ma, sa = table.clone(), m0.clone(), s0.clone()
         ops.spd_radam_step_(ta, grad, ma, sa, pows, 1e-2, (0.9, 0.999), 1e-7, 0.0)
-        return [ops.spd_egrad2rgrad(table, grad), t, ta, ma, sa]
+        # one map and one step of the geodesic family (spd_expmap_kernel.hpp, behind the same gate): the geodesic between the rows
+        # and their neighbours at t = 0.3 (the map that runs both log1p and expm1), the step along the geodesic
+        te = table.clone()
+        ops.spd_rsgd_step_exp_(te, grad, 1e-2)
+        return [ops.spd_egrad2rgrad(table, grad), t, ta, ma, sa, ops.spd_geodesic(table, table.flip(0).contiguous(), 0.3), te]
 
     fast = run()
     with _OneLane(SPD_TABLE, "spd", n):

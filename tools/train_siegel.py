@@ -124,11 +124,14 @@ def train(args, log=print):
         raise SystemExit("--retraction exp: RiemannianSGD or RiemannianAdam in the classic single-GPU loop only (the graphed, fused "
                          "and distributed steps embed the linear retraction)")
     model = Model(args).to(dev)
-    if args.optim == "radam":        # train.py:69-70
-        opt = RiemannianAdam(model.parameters(), lr=args.learning_rate * world, eps=1e-7, stabilize=None, retraction=retraction)
-    else:                            # train.py:66-68
-        opt = RiemannianSGD(model.parameters(), lr=args.learning_rate * world, weight_decay=0.0, stabilize=None,
-                            retraction=retraction)
+    try:
+        if args.optim == "radam":        # train.py:69-70
+            opt = RiemannianAdam(model.parameters(), lr=args.learning_rate * world, eps=1e-7, stabilize=None, retraction=retraction)
+        else:                            # train.py:66-68
+            opt = RiemannianSGD(model.parameters(), lr=args.learning_rate * world, weight_decay=0.0, stabilize=None,
+                                retraction=retraction)
+    except NotImplementedError as e:     # (--retraction exp on a table without the kernel, e.g. spd with radam)
+        raise SystemExit(f"--retraction {retraction} --optim {args.optim} --manifold {args.manifold}: {e}")
     radius = upper = None
     eval_hops = hops
     label_max = None
@@ -314,7 +317,7 @@ def parser():
     ap.add_argument("--optim", default="rsgd", choices=["rsgd", "radam"])
     ap.add_argument("--retraction", default="linear", choices=["linear", "exp"],
                     help="linear = the reference's projx(x + u); exp = the step follows the geodesic (rsgd: sympa_rsgd_step_exp; radam: "
-                         "sympa_radam_step_exp, exp_avg parallel-transported; upper and bounded, dims <= 8), in the classic loop with "
+                         "sympa_radam_step_exp, exp_avg parallel-transported; upper and bounded, dims <= 8; spd with rsgd: sympa_spd_rsgd_step_exp), in the classic loop with "
                          "the eager optimiser")
     ap.add_argument("--max_grad_norm", type=float, default=50.0)
     ap.add_argument("--batch_size", type=int, default=512)
